@@ -16,7 +16,18 @@ holds observer rows [N*r/G, N*(r+1)/G) of the same 65,536-member cluster on GPU 
 cross-shard message moves over RCCL point-to-point (xGMI) inside libswimsim. Total work is fixed, so
 "scaling" is "strong".
 
-The JSON line carries:
+A plain run (`--gpus G --steps K --warmup W`) does only what the headline figure needs: set up, warm up, time
+the K rounds, write --dump-outputs if given, print the line (metric, value, unit, ms_per_step, the window). Everything
+else the benchmark measures is behind --full: the HIP-event kernel times and roofline, the protocol counters and
+exchange block, the profile marks around the window, the CPU baseline, the hash ring, config4's rounds to heal.
+
+--dump-outputs DIR: after the timed rounds, what a caller of the timed path reads back, as DIR/<name>.npy (float64,
+every value exact): checksums, last_targets, counters, digest (three u64 as six 32-bit halves, high then low), and
+the status / incarnation rows of 16 observers drawn with a fixed seed (rows_observers names them). With --gpus N > 1
+each rank writes its own shard as <name>_rank<r>.npy. The workloads are seeded, so the arrays of two runs with the
+same arguments are equal.
+
+With --full the JSON line also carries:
   roofline     : the kernel with the most device time (rank 0): units per launch (rows hashed, changes
                  merged; counted on the device over the timed rounds) x SURVEY.md §8(d)'s bytes per unit
                  = algorithmic bytes per launch, / its average launch time (HIP events on the engine's own
@@ -28,7 +39,7 @@ The JSON line carries:
   cpu_baseline : the C oracle on the GPU box's host cores (rank 0, N=1 only) at the GPU line's N, bounded sample.
 
 --workload (1 GPU; default config3, the driver's line): the other BASELINE.json configs measured the same way, each a
-line of its own (not the headline): config2 (4,096 members, 1 % churn per round), config4 (16,384 members, 2-way
+line of its own (not the headline; --full adds the same blocks as above): config2 (4,096 members, 1 % churn per round), config4 (16,384 members, 2-way
 partition then heal_partition; the line adds the rounds from the heal to convergence, from an untimed replay),
 selfstart (16,384 members that know only themselves and two seed members: full syncs and reverse full syncs) and
 config5 (incarnation bursts, 10 % of 65,536 members every 20 rounds; 262,144 needs 8 GPUs). Their roofline adds the
@@ -280,6 +291,35 @@ def cpu_baseline(gpu_window, members, seconds_budget=50.0):
     return json.loads(out.stdout.strip().splitlines()[-1])
 
 
+DUMP_ROWS = 16          # observer rows in a dump: 16 x 65,536 members x 2 float64 columns = 16 MiB, under 64 MB in all
+DUMP_SEED = 20240607
+
+
+def dump_outputs(out_dir, eng, rank, ws):
+    """--dump-outputs: what a caller of the timed path reads back after its last round, as float64 .npy files (u32,
+    i32, u8 and the int64 incarnations, epoch milliseconds below 2^53, are all exact in float64). The whole of the
+    per-observer vectors of this rank's shard, and the rows of DUMP_ROWS of its observers drawn with a fixed seed."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    suffix = f"_rank{rank}" if ws > 1 else ""
+    d0, d1, d2 = eng.digest()
+    counters = eng.counters()
+    pick = np.sort(np.random.default_rng(DUMP_SEED).choice(eng.nl, size=min(DUMP_ROWS, eng.nl), replace=False)) + eng.lo
+    rows = [eng.row(int(o)) for o in pick]
+    arrays = {
+        "checksums": eng.checksums(),
+        "last_targets": eng.last_targets(),
+        "counters": np.array([counters[k] for k in sorted(counters)]),
+        "digest": np.array([h for d in (d0, d1, d2) for h in (d >> 32, d & 0xFFFFFFFF)]),
+        "rows_observers": pick,
+        "rows_status": np.stack([st for st, _ in rows]),
+        "rows_incarnation": np.stack([inc for _, inc in rows]),
+    }
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"), np.asarray(a).astype(np.float64))
+
+
 def free_port():
     with socket.socket() as s:
         s.bind(("127.0.0.1", 0))
@@ -363,12 +403,12 @@ def rounds_to_heal(swimsim, wl, device, tuning, heal_round):
         eng.close()
 
 
-def workload_line(args, wl, n, dt, value, live_mr, dominant, entries, kt, counters, units, eng):
-    """the JSON line of a --workload other than config3 (1 GPU): the same fields as the headline line, the dense merges'
-    roofline entry beside the dominant kernel, and (config4) the rounds from the heal to convergence"""
+def workload_line(args, wl, n, dt, value, live_mr, detail, eng):
+    """the JSON line of a --workload other than config3 (1 GPU): the same fields as the headline line and, with --full
+    (detail = dominant family, roofline entries, kernel times, counters, units), the dense merges' roofline entry beside
+    the dominant kernel and (config4) the rounds from the heal to convergence"""
     import swimsim
 
-    dom = entries.get(dominant) or {}
     line = {
         "metric": f"simulated member-rounds/sec, {WORKLOADS[args.workload][1]} at {n} members",
         "value": round(value, 1), "unit": "member-rounds/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
@@ -378,6 +418,12 @@ def workload_line(args, wl, n, dt, value, live_mr, dominant, entries, kt, counte
         "config": {"workload": f"{WORKLOADS[args.workload][1]}: {wl.name}, rounds {args.warmup}-{args.warmup + args.steps - 1} "
                                "timed", "members": n, "rounds_timed": args.steps, "live_member_rounds": live_mr,
                    "parallelism": "1 GPU"},
+    }
+    if detail is None:
+        return line
+    dominant, entries, kt, counters, units = detail
+    dom = entries.get(dominant) or {}
+    line.update({
         "roofline": {"bound": dom_bound(dominant, dom), **dom, "dominant_family": dominant,
                      "kernels": {f: e for f, e in entries.items() if e and f != dominant},
                      "merge_kernel": entries.get("recv_merge"), "dense_merge_kernel": entries.get("rfs_merge")},
@@ -387,7 +433,7 @@ def workload_line(args, wl, n, dt, value, live_mr, dominant, entries, kt, counte
         "dense_merges": {k: int(v) for k, v in units.items() if k in ("dense_resp", "dense_jobs", "jobs_applied",
                                                                      "dense_heal")},
         "checksum_paths": eng.checksum_path_stats(),
-    }
+    })
     if line["roofline"]["bound"] == "valu":
         line["roofline"]["bound_frac"] = (dom.get("valu") or {}).get("frac")
     if args.workload == "config4":
@@ -406,19 +452,26 @@ def main():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--members", type=int, default=0)        # 0: the workload's default (config3: 65,536)
     ap.add_argument("--workload", choices=sorted(WORKLOADS), default="config3")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-ring", action="store_true")
+    # everything beyond the headline figure: kernel times and roofline, counters, CPU baseline, hash ring, rounds to heal
+    ap.add_argument("--full", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None)   # the last timed step's read-back as DIR/<name>.npy
+    ap.add_argument("--no-cpu-baseline", action="store_true")   # (--full only)
+    ap.add_argument("--no-ring", action="store_true")           # (--full only)
     # diagnostics: every rank on cuda:0, shards exchanging through the gloo host transport instead of
     # RCCL (lets the multi-process path run on a one-GPU machine); never used for reported numbers
     ap.add_argument("--host-transport", action="store_true")
     # the reference-row checksum path (swimsim_tuning.cs_ref: 0 off, 1 wide launches; default: the library's)
     ap.add_argument("--cs-ref", type=int, default=-1)
     ap.add_argument("--cs-async-rows", type=int, default=-1)   # side-stream checksum launches up to this many rows
-    ap.add_argument("--time-all", action="store_true")   # HIP events around every kernel family (diagnostics)
+    ap.add_argument("--time-all", action="store_true")   # --full: HIP events around every kernel family (diagnostics)
     # test hook: the ranks report (rank, world size) and exit before any GPU call
     ap.add_argument("--launch-check", action="store_true")
     args = ap.parse_args()
 
+    if args.time_all and not args.full:
+        ap.error("--time-all needs --full")
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps needs at least 1, --warmup at least 0")
     if args.members <= 0:
         args.members = WORKLOADS[args.workload][0]
     if args.gpus > 1 and args.workload != "config3":
@@ -485,9 +538,10 @@ def main():
 
     for r in range(args.warmup):
         eng.step(1, wl.events_for(r))
-    # (level 2: HIP events around the roofline's kernels only; every other family's event pair cost the window ~10 us)
-    eng.enable_timing(1 if args.time_all else 2 if args.workload == "config3" else 3)
-    if rank == 0:
+    if args.full:
+        # (level 2: HIP events around the roofline's kernels only; every other family's event pair cost the window ~10 us)
+        eng.enable_timing(1 if args.time_all else 2 if args.workload == "config3" else 3)
+    if args.full and rank == 0:
         eng.profile_mark(MARK_BEGIN)    # rocprofv3 counter passes are cut to the launches between the two marks
     barrier()
     t0 = time.perf_counter()
@@ -500,15 +554,18 @@ def main():
 
         dt = sd.max_over_ranks(dt)
 
-    if rank == 0:
-        eng.profile_mark(MARK_END)
-    kt = eng.kernel_times()
-    units = eng.kernel_units()
-    counters = eng.counters()
-    shard = eng.shard_info()
-    eng.enable_timing(False)
-    if ws > 1:
-        counters = sd.reduce_counters(counters)
+    if args.full:
+        if rank == 0:
+            eng.profile_mark(MARK_END)
+        kt = eng.kernel_times()
+        units = eng.kernel_units()
+        counters = eng.counters()
+        shard = eng.shard_info()
+        eng.enable_timing(False)
+        if ws > 1:
+            counters = sd.reduce_counters(counters)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, eng, rank, ws)
     workload = {"members": n, "steps": args.steps, "warmup": args.warmup, "gpus": ws}
     if args.workload != "config3":
         workload["workload"] = args.workload
@@ -517,13 +574,16 @@ def main():
         timed_first, timed_last = args.warmup, total_rounds - 1
         live_mr = live_member_rounds(wl, timed_first, timed_last)
         value = live_mr / dt
-        dominant = max(kt.items(), key=lambda kv: kv[1]["avg_ms"] * kv[1]["launches"])[0]
-        entries = {f: add_pmc(roofline_entry(f, kt, units, n), f, workload) for f in FAMILY_KERNEL}
-        dom = entries.get(dominant) or {}
+        detail = None
+        if args.full:
+            dominant = max(kt.items(), key=lambda kv: kv[1]["avg_ms"] * kv[1]["launches"])[0]
+            entries = {f: add_pmc(roofline_entry(f, kt, units, n), f, workload) for f in FAMILY_KERNEL}
+            dom = entries.get(dominant) or {}
+            detail = (dominant, entries, kt, counters, units)
         in_window = timed_first <= KILL_ROUND <= timed_last
         faulty_from = KILL_ROUND + 25       # first suspicions at KILL_ROUND; their timers fire 25 rounds later
         if args.workload != "config3":
-            line = workload_line(args, wl, n, dt, value, live_mr, dominant, entries, kt, counters, units, eng)
+            line = workload_line(args, wl, n, dt, value, live_mr, detail, eng)
             sys.stdout.flush()
             emit(line)
             return
@@ -548,31 +608,35 @@ def main():
                        "members": n, "rounds_timed": args.steps, "live_member_rounds": live_mr,
                        "parallelism": (f"observer-row shards x{ws} over " + ("host transport (diagnostic)" if args.host_transport
                                                                               else "RCCL")) if ws > 1 else "1 GPU"},
-            "roofline": {"bound": dom_bound(dominant, dom), **dom, "dominant_family": dominant,
-                         "kernels": {f: e for f, e in entries.items() if e and f != dominant},
-                         "merge_kernel": entries.get("recv_merge")},
-            "kernel_ms": {k: round(v["avg_ms"] * v["launches"], 3) for k, v in kt.items() if v["launches"]},
-            "kernel_ms_note": ("HIP-event device time over the window of every kernel family" if args.time_all else
-                               "HIP-event device time over the window of the families the roofline reports; the others "
-                               "are not timed in the window (bench.py --time-all; profiles/ holds rocprofv3 kernel stats)"),
-            "counters": counters,
-            "checksum_paths": eng.checksum_path_stats(),
-            "deferred_decisions": {k: int(units.get(k, 0)) for k in ("defer", "defer_eq", "defer_rep", "defer_undo",
-                                                                              "defer_norow")},
         }
-        if line["roofline"]["bound"] == "valu":
-            line["roofline"]["bound_frac"] = (dom.get("valu") or {}).get("frac")
-            line["roofline"]["frac_basis"] = "achieved / peak / frac: HBM bytes of SURVEY.md §8(d); the bound is VALU issue (bound_frac)"
-        if ws > 1:
-            line["exchange"] = {"bytes_rank0": shard["exchanged_bytes"], "exchanges_rank0": shard["exchanges"],
-                                "bytes_per_round_rank0": round(shard["exchanged_bytes"] / max(1, total_rounds), 1),
-                                "exchanges_per_round_rank0": round(shard["exchanges"] / max(1, total_rounds), 2),
-                                "host_syncs_per_exchange_rank0": round(shard.get("exchange_host_syncs", 0) /
-                                                                       max(1, shard["exchanges"]), 2)}
-        if ws == 1 and not args.no_cpu_baseline:
-            line["cpu_baseline"] = cpu_baseline(f"{n}:{args.warmup}:{args.steps}", n)
-        if ws == 1 and not args.no_ring:
-            line["hashring"] = ring_bench(n)
+        if args.full:
+            line.update({
+                "roofline": {"bound": dom_bound(dominant, dom), **dom, "dominant_family": dominant,
+                             "kernels": {f: e for f, e in entries.items() if e and f != dominant},
+                             "merge_kernel": entries.get("recv_merge")},
+                "kernel_ms": {k: round(v["avg_ms"] * v["launches"], 3) for k, v in kt.items() if v["launches"]},
+                "kernel_ms_note": ("HIP-event device time over the window of every kernel family" if args.time_all else
+                                   "HIP-event device time over the window of the families the roofline reports; the others "
+                                   "are not timed in the window (bench.py --full --time-all; profiles/ holds rocprofv3 "
+                                   "kernel stats)"),
+                "counters": counters,
+                "checksum_paths": eng.checksum_path_stats(),
+                "deferred_decisions": {k: int(units.get(k, 0)) for k in ("defer", "defer_eq", "defer_rep", "defer_undo",
+                                                                                  "defer_norow")},
+            })
+            if line["roofline"]["bound"] == "valu":
+                line["roofline"]["bound_frac"] = (dom.get("valu") or {}).get("frac")
+                line["roofline"]["frac_basis"] = "achieved / peak / frac: HBM bytes of SURVEY.md §8(d); the bound is VALU issue (bound_frac)"
+            if ws > 1:
+                line["exchange"] = {"bytes_rank0": shard["exchanged_bytes"], "exchanges_rank0": shard["exchanges"],
+                                    "bytes_per_round_rank0": round(shard["exchanged_bytes"] / max(1, total_rounds), 1),
+                                    "exchanges_per_round_rank0": round(shard["exchanges"] / max(1, total_rounds), 2),
+                                    "host_syncs_per_exchange_rank0": round(shard.get("exchange_host_syncs", 0) /
+                                                                           max(1, shard["exchanges"]), 2)}
+            if ws == 1 and not args.no_cpu_baseline:
+                line["cpu_baseline"] = cpu_baseline(f"{n}:{args.warmup}:{args.steps}", n)
+            if ws == 1 and not args.no_ring:
+                line["hashring"] = ring_bench(n)
         sys.stdout.flush()
         emit(line)
     if ws > 1:

@@ -2,11 +2,12 @@
 # GPU session script: each step under its own time limit; stop at the first failing step.
 # usage: run_gpu.sh [tests|smoke|bench|prof|pmc|calib|curve|all ...]   (several modes run in the order given)
 # BENCH_ARGS defaults to the driver's round-end command (--steps 20 --warmup 5); prof and pmc profile
-# exactly that command, so profiles/ figures and the bench line describe the same workload.
+# exactly that command, so profiles/ figures and the bench line describe the same workload. Every bench.py
+# call here passes --full: the line's roofline and CPU baseline, and the profile marks that cut the window.
 cd "$GRAFT_REPO_ROOT" || exit 1
 mkdir -p gpurun_out
 export TMPDIR=/tmp
-BENCH_ARGS=${BENCH_ARGS:---steps 20 --warmup 5}
+BENCH_ARGS="--full ${BENCH_ARGS:---steps 20 --warmup 5}"
 PROF_ARGS="$BENCH_ARGS --no-cpu-baseline --no-ring"
 WL=${WL:-65536:20:5:1}
 [ $# -eq 0 ] && set -- all
@@ -55,7 +56,7 @@ for mode in "$@"; do
     ;;
   bench2)
     timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 \
-      --master-port 29511 bench.py --gpus 2 --members 2048 --steps 30 --warmup 10 --host-transport \
+      --master-port 29511 bench.py --full --gpus 2 --members 2048 --steps 30 --warmup 10 --host-transport \
       > gpurun_out/bench2.json 2> gpurun_out/bench2.err
     rc=$?; echo "bench2 rc=$rc" >> gpurun_out/bench2.err; [ $rc -eq 0 ] || exit $rc
     ;;

@@ -56,7 +56,7 @@ def _bench(extra, timeout=300):
     repo = os.path.dirname(HERE)
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     out = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--members", "4096", "--warmup", "6",
-                          "--steps", "8", "--no-cpu-baseline", "--no-ring"] + extra, env=env, cwd=repo,
+                          "--steps", "8", "--full", "--no-cpu-baseline", "--no-ring"] + extra, env=env, cwd=repo,
                          capture_output=True, text=True, timeout=timeout)
     assert out.returncode == 0, (out.stdout + out.stderr)[-4000:]
     from test_bench_launch import json_objects

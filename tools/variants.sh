@@ -1,7 +1,8 @@
 #!/bin/bash
 # Diagnostics: run every variants/*.so build (SWIMSIM_LIB) one after another.
 #   VAR_MODE=cs (default): checksum microbench (CS_MODES, default 0,2)
-#   VAR_MODE=bench       : bench.py --no-cpu-baseline (prints value and kernel_ms)
+#   VAR_MODE=bench       : bench.py --full --no-cpu-baseline (prints value and kernel_ms)
+BENCH_ARGS="--full ${BENCH_ARGS:---steps 20 --warmup 5}"
 cd "$GRAFT_REPO_ROOT" || exit 1
 mkdir -p gpurun_out
 for v in variants/*.so; do
