@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define SWIMSIM_ABI_VERSION 5
+#define SWIMSIM_ABI_VERSION 6
 
 enum {
     SWIMSIM_OK = 0,
@@ -92,6 +92,13 @@ typedef struct swimsim_tuning {
                                  launches of 1,024 rows and more take that path (4,097 by default); 1024 = one
                                  generation of side-stream snapshot slots (phase C waits for the previous round's side
                                  launch); default 0. Results are identical with 4, 8, 16, 32, 64, 128, 256 and 1024. */
+    int32_t defer_test;       /* tests only (ABI 6): which ways a deferred full-sync decision may be settled without a hash
+                                 (DESIGN.md §5), bits: 1 = a still-clean sender's current row is not compared directly;
+                                 2 = no checksum representatives; 4 = no undo log; 8 = the undo log holds 2 entries per
+                                 row instead of 64; 16 = the representative table has one slot (every checksum
+                                 collides, the last store wins, the losing decisions fall through). Results are
+                                 identical with every combination; <= 0 (default, and the 0 an older caller's
+                                 zero-initialised struct reads): the production engine */
 } swimsim_tuning;
 /* Environment, read at swimsim_create (A/B experiments; results are identical either way): SWIMSIM_SYNC_SPIN=0 waits for
  * the main stream's host round trips in the runtime's stream wait instead of polling an event; SWIMSIM_SIDE2=0 runs both

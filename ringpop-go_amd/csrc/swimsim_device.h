@@ -46,10 +46,14 @@ enum Counter {
     // deferred full-sync decisions (k_defer_eq): all, settled by row equality, with no issue-time row to compare with
     // (C_X_DEFER_REP: settled against a clean row of the sender's issue-time checksum, k_cs_reps)
     // (C_X_DEFER_UNDO: settled against the sender's row with this phase's logged merges undone, d.ulog)
-    C_X_DEFER, C_X_DEFER_EQ, C_X_DEFER_NOROW, C_X_DEFER_REP, C_X_DEFER_UNDO, C_NALL
+    C_X_DEFER, C_X_DEFER_EQ, C_X_DEFER_NOROW, C_X_DEFER_REP, C_X_DEFER_UNDO,
+    // the "differ" side of the two shortcuts (the comparison ran and found the rows different: the decision hashes),
+    // deferred decisions that ended as a full sync (k_recv_finish), undo branches that met a log past its cap, and
+    // decisions whose sender's C_o was known at issue (every one that is not a pending sender's)
+    C_X_DEFER_REP_DIFF, C_X_DEFER_UNDO_DIFF, C_X_DEFER_FS, C_X_DEFER_UNDO_OVER, C_X_DEFER_CLEAN, C_NALL
 };
 
-constexpr int CTR_SHARDS = 64, CTR_STRIDE = 48;   // d.ctr is [CTR_SHARDS][CTR_STRIDE] u64
+constexpr int CTR_SHARDS = 64, CTR_STRIDE = 64;   // d.ctr is [CTR_SHARDS][CTR_STRIDE] u64
 static_assert(C_NALL + 8 <= CTR_STRIDE, "counter block too small (8 diagnostic slots follow C_NALL)");
 constexpr uint32_t POOL_SHARDS = 64, POOL_CUR_STRIDE = 16;   // d.pool_cur is [POOL_SHARDS][POOL_CUR_STRIDE] u64
 
@@ -151,14 +155,18 @@ struct DS {
     // them: ucl = every colx column in member order (ucnt[0] of them) with its hot slot uhk (SRC_NONE: none), ucold =
     // the colx columns without a hot slot (ucnt[1], any order). Rows are equal iff equal at the hot slots and ucold.
     uint32_t *ucl, *uhk, *ucold, *ucnt;
-    // the words a receive phase's merges overwrote (k_recv, phases D and Q2): per row up to ULOG_CAP {member, old word}
-    // in apply order and their count (ULOG_CAP + 1: more, not usable). A row that was clean when it issued its message
-    // and changed only in the phase since is its issue-time row with the first old word of each logged member restored
-    // (k_defer_eq); nullptr: off
+    // the words a receive phase's merges overwrote (k_recv, phases D and Q2): per row up to ulog_cap {member, old word}
+    // in apply order and their count (ulog_cap + 1: more, not usable; 0 for every row when the phase starts, so a row
+    // that receives nothing has an empty log). A row that was clean when it issued its message and changed only in the
+    // phase since is its issue-time row with the first old word of each logged member restored (k_defer_eq, DESIGN.md
+    // §5); nullptr: off
     uint2 *ulog;
     uint32_t *ulog_cnt;
+    uint32_t ulog_cap;        // entries a row's log may hold: ULOG_CAP (tests: 2, swimsim_tuning.defer_test bit 8)
+    uint32_t defer_test;      // swimsim_tuning.defer_test (tests: which ways k_defer_eq may settle a decision); 0
 };
-constexpr uint32_t ULOG_CAP = 64;
+constexpr uint32_t ULOG_CAP = 64;   // storage stride of a row's log, and the most ulog_cap can be: k_defer_eq holds a
+                                    // log in one wave's lanes
 
 // hot slot of member m, SRC_NONE when m has none (or hot columns are off)
 __device__ __forceinline__ uint32_t hot_slot(const DS &d, uint32_t m) { return d.hidx ? d.hidx[m] : SRC_NONE; }

@@ -350,7 +350,7 @@ struct swimsim {
     uint32_t *defer_cnt = nullptr;
     uint8_t *defer_eq = nullptr;                  // deferred decision settled by row equality
     unsigned long long *rep_tab = nullptr;        // checksum representatives (k_cs_reps), rep_mask + 1 entries
-    unsigned long long *fp_tab = nullptr;         // phase-C dedup groups (k_fp_table): two tables of 2 (rep_mask + 1)
+    unsigned long long *fp_tab = nullptr;         // phase-C dedup groups (k_fp_table): two tables of 2 rep_slots(NL)
     uint32_t rep_mask = 0, rep_gen = 0;
     uint32_t *exh_list = nullptr, *exh_cnt = nullptr, *scratch = nullptr;
     uint8_t *need = nullptr, *fsflag = nullptr;
@@ -394,6 +394,7 @@ struct swimsim {
     uint64_t csr_launches = 0;
     uint32_t csr_side_min = 4097;                 // side launches of at least this many rows take the path (csr2)
     int fault_inject = 0;                         // swimsim_tuning.fault_inject (tests)
+    int defer_test = 0;                           // swimsim_tuning.defer_test (tests)
     bool colx_stale = false;                      // raw row writes marked every column: rebuilt at the next step
 #ifdef SWIMSIM_DIAG
     // reference-row checksum path (swimsim_checksum_delta.hip), allocated at its first launch
@@ -1190,7 +1191,7 @@ int checksum_dirty(swimsim *h, int mode, bool async = false) {
         // groups by fingerprint without sorting (k_fp_table: the smallest {tag, row} offer wins a slot, so the heads and
         // the rows hashed are the same in every run of one command, whatever order k_list's atomics left the list in)
         const unsigned long long keymask = (h->fault_inject & 8) ? 7ull : ~0ull;
-        const uint32_t fmask = 2u * (h->rep_mask + 1u) - 1u;       // (two tables of 4 NL slots or more)
+        const uint32_t fmask = 2u * rep_slots(h->NL) - 1u;      // (two tables of 4 NL slots or more)
         HIPCHK(h, hipMemsetAsync(h->fp_tab, 0xFF, (size_t)(fmask + 1) * 2 * 8, h->s));
         for (int pass = 0; pass < 2; pass++)
             hipLaunchKernelGGL(k_fp_table, dim3(blocks_for_threads(n)), dim3(256), 0, h->s, h->d, h->list, n, h->fp_tab,
@@ -1308,8 +1309,9 @@ int run_waves(swimsim *h, int phase, uint32_t nruns_valid, uint32_t maxcount) {
     hipMemsetAsync(h->defer_cnt, 0, 4, h->s);
     {
         Scope sc(h, F_SORT);
-        hipLaunchKernelGGL(k_pair_info, dim3(blocks_for_threads(h->inbox_n)), dim3(256), 0, h->s, h->d, h->vals_out, h->inbox_n,
-                           phase, a.sdesc, a.sI, a.sC, a.sS, h->pinfo);
+        // (it also empties every local row's undo log for this phase, hence at least NL threads)
+        hipLaunchKernelGGL(k_pair_info, dim3(blocks_for_threads(std::max(h->inbox_n, h->NL))), dim3(256), 0, h->s, h->d,
+                           h->vals_out, h->inbox_n, phase, a.sdesc, a.sI, a.sC, a.sS, h->pinfo);
     }
     {
         Scope sc(h, F_RECV);
@@ -1811,6 +1813,7 @@ int swimsim_create(const swimsim_config *cfg, swimsim_t **out) {
     if (tun && tun->cs_narrow_rows >= 0) h->cs_narrow_rows = (uint32_t)tun->cs_narrow_rows;
     if (tun && tun->cs_ref >= 0) h->csr_mode = tun->cs_ref;
     if (tun && tun->fault_inject > 0) h->fault_inject = tun->fault_inject;
+    if (tun && tun->defer_test > 0) h->defer_test = tun->defer_test;
     if (h->fault_inject & 32) h->csr_ecap = 24;      // (tests: rows whose exception entries end within CSR_EREG of the cap)
     if (h->fault_inject & 256) h->csr_side_min = 1024;   // (tests: side launches of 1,024 rows and more take the path)
     if (const char *v = getenv("SWIMSIM_SYNC_SPIN")) h->sync_spin = atoi(v) != 0;   // (experiment: 0 = the runtime's wait)
@@ -1963,8 +1966,9 @@ int swimsim_create(const swimsim_config *cfg, swimsim_t **out) {
         (rc = dalloc(h, &h->fsflag, KC, "fsflag")) || (rc = dalloc(h, &h->hsics, 4, "hsics")) ||
         (rc = dalloc(h, &h->npairs, 1, "npairs")))
         return bail(rc);
-    h->rep_mask = rep_slots(h->NL) - 1u;
-    hipMemset(h->d.ulog_cnt, 0xFF, (size_t)h->NL * 4);            // (no row has a usable log before its first receive)
+    h->rep_mask = (h->defer_test & 16) ? 0u : rep_slots(h->NL) - 1u;   // (tests: one slot, every checksum collides)
+    h->d.ulog_cap = (h->defer_test & 8) ? 2u : ULOG_CAP;               // (tests: logs past the cap at small sizes)
+    h->d.defer_test = (uint32_t)h->defer_test;
     hipMemset(h->rep_tab, 0, (size_t)rep_slots(h->NL) * 8);      // (generation 0: every entry empty)
     h->evcap = 4 * h->N + 64;
     if ((rc = dalloc(h, &h->evbuf, h->evcap, "events")) || (rc = dalloc(h, &h->ev_applied, h->evcap, "ev_applied")))
@@ -2824,11 +2828,14 @@ int swimsim_kernel_units(swimsim_t *h, const char **names, double *values, size_
                                "bitmap_words_per_row", "diag_stamp0", "diag_stamp1", "diag_stamp2", "diag_stamp3",
                                "hot_slots", "diag_stamp4", "diag_stamp5", "diag_stamp6", "diag_stamp7",
                                "dense_resp", "dense_jobs", "jobs_applied", "dense_heal", "defer", "defer_eq", "defer_norow",
-                               "defer_rep", "defer_undo"};
+                               "defer_rep", "defer_undo", "defer_rep_diff", "defer_undo_diff", "defer_fs",
+                               "defer_undo_over", "defer_clean"};
     const int ki[] = {C_X_CS_ROWS, C_X_CS_ROWS_N, C_X_CS_DUP, C_X_MERGED, C_X_APPLIED, C_X_RISSUED, C_X_RCALLS,
                       C_X_MERGED_R, C_X_APPLIED_R, C_X_BUMPED, C_X_ISSUED, -1, C_NALL, C_NALL + 1, C_NALL + 2, C_NALL + 3,
                       -2, C_NALL + 4, C_NALL + 5, C_NALL + 6, C_NALL + 7, C_X_DENSE_RESP, C_X_DENSE_JOBS, C_X_JOBS_APPLIED,
-                      C_X_DENSE_HEAL, C_X_DEFER, C_X_DEFER_EQ, C_X_DEFER_NOROW, C_X_DEFER_REP, C_X_DEFER_UNDO};
+                      C_X_DENSE_HEAL, C_X_DEFER, C_X_DEFER_EQ, C_X_DEFER_NOROW, C_X_DEFER_REP, C_X_DEFER_UNDO,
+                      C_X_DEFER_REP_DIFF, C_X_DEFER_UNDO_DIFF, C_X_DEFER_FS, C_X_DEFER_UNDO_OVER, C_X_DEFER_CLEAN};
+    static_assert(sizeof(kn) / sizeof(kn[0]) == sizeof(ki) / sizeof(ki[0]), "one counter per name");
     uint32_t hot = 0;                                              // hot slots in use now (not a delta)
     if (h->d.hot_cnt) {
         HIPCHK(h, hipMemcpyAsync(&hot, h->d.hot_cnt, 4, hipMemcpyDeviceToHost, h->s));

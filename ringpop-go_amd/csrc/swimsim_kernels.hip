@@ -389,7 +389,7 @@ __device__ __forceinline__ void wave_merge_body(const DS &d, uint32_t ol, uint32
                     const bool ap = acc.napp != before;
                     const unsigned long long b = __ballot(ap);
                     const uint32_t at = *ulog + (uint32_t)__popcll(b & lanemask_lt());
-                    if (ap && at < ULOG_CAP) d.ulog[(size_t)ol * ULOG_CAP + at] = make_uint2(rec_m(rec[u]), cur[u]);
+                    if (ap && at < d.ulog_cap) d.ulog[(size_t)ol * ULOG_CAP + at] = make_uint2(rec_m(rec[u]), cur[u]);
                     *ulog += (uint32_t)__popcll(b);
                 }
             }
@@ -397,7 +397,7 @@ __device__ __forceinline__ void wave_merge_body(const DS &d, uint32_t ol, uint32
     } else if (md.kind == 1) {
         wave_merge_dense(d, ol, o, md, now_e, sched_r, acc);
         if (dctr >= 0 && lane_id() == 0) ctr_add(d, dctr, 1ull);
-        if (ulog) *ulog = ULOG_CAP + 1u;                           // (not logged: the row's issue-time words are lost)
+        if (ulog) *ulog = d.ulog_cap + 1u;                          // (not logged: the row's issue-time words are lost)
     }
     __threadfence_block();
 }
@@ -1377,6 +1377,9 @@ struct RecvArgs {
 __global__ void k_pair_info(const DS d, const uint32_t *vals, uint32_t n, int phase, const MsgDesc *sdesc, const uint32_t *sI,
                             const uint32_t *sC, const uint32_t *sS, uint4 *pinfo) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    // the phase's undo logs start empty, also those of the rows that will receive nothing (k_defer_eq reads a sender's
+    // count whether or not it was a receiver); the grid covers max(n, NL) threads
+    if (d.ulog_cnt && i < d.NL) d.ulog_cnt[i] = 0u;
     if (i >= n) return;
     const uint32_t v = vals[i], sender = phase == 0 ? v : v / d.K;
     if (sender >= d.N) return;                                     // (sentinel keys: no receiver reads them)
@@ -1481,7 +1484,7 @@ __global__ void __launch_bounds__(256, RECV_MIN_WAVES) k_recv(DS d, RecvArgs a) 
         const uint32_t pair = off + w;
         recv_one_pre(d, a, key, a.pinfo[2 * (size_t)pair], a.pinfo[2 * (size_t)pair + 1], pair, nslots, p);
     }
-    if (d.ulog_cnt && lane_id() == 0) d.ulog_cnt[key - d.lo] = min(p.ulog, ULOG_CAP + 1u);
+    if (d.ulog_cnt && lane_id() == 0) d.ulog_cnt[key - d.lo] = min(p.ulog, d.ulog_cap + 1u);
 }
 
 // DS::colx from the rows themselves (one lane per column, a wave's 64 columns in two bitmap words): after raw row
@@ -1608,8 +1611,9 @@ __device__ bool wave_rows_differ(const DS &d, const uint32_t *a, const uint32_t 
 }
 
 // one wave: does snapshot a differ from live row b as it was before its logged merges (the first logged old word of each
-// member restored; nlog <= ULOG_CAP entries of log, members inside the divergent columns: every row-word write marks its
-// column)? Only over the divergent columns; false when they are more than N/4 (the caller hashes instead)
+// member restored; nlog <= d.ulog_cap <= 64 entries of log, one per lane, members inside the divergent columns: every
+// row-word write marks its column)? Only over the divergent columns; false when they are more than N/4 (the caller
+// hashes instead)
 __device__ bool wave_rows_differ_undo(const DS &d, const uint32_t *a, const uint32_t *b, const uint2 *log, uint32_t nlog,
                                       bool &done) {
     const uint32_t lane = lane_id();
@@ -1681,12 +1685,13 @@ __global__ void k_defer_eq(DS d, const uint4 *defer, const uint32_t *defer_cnt, 
     const uint32_t ri = e.x & 0x7FFFFFFFu, sender = phase == 1 ? ri / d.K : ri;
     const uint32_t *srow = nullptr;
     bool viarep = false;
+    const uint32_t dt = d.defer_test;                              // (tests: bits 1, 2, 4 skip a way each)
     if (phase != 2) {
         if (e.w & 0x80000000u) {
             if (!(e.z & 0x80000000u)) srow = d.dense + (size_t)e.z * d.NP;
-        } else if (sender >= d.lo && sender < d.lo + d.NL && !d.dirty[sender - d.lo]) {
+        } else if (!(dt & 1u) && sender >= d.lo && sender < d.lo + d.NL && !d.dirty[sender - d.lo]) {
             srow = d.mw + (size_t)(sender - d.lo) * d.NP;
-        } else if (tab) {                                          // C_o = e.z known: a representative of it
+        } else if (tab && !(dt & 2u)) {                            // C_o = e.z known: a representative of it
             const uint32_t r = rep_find(d, tab, mask, gen, e.z);
             if (r != SRC_NONE) {
                 srow = d.mw + (size_t)r * d.NP;
@@ -1694,14 +1699,16 @@ __global__ void k_defer_eq(DS d, const uint4 *defer, const uint32_t *defer_cnt, 
             }
         }
     }
-    bool same = false, viaundo = false;
+    bool same = false, viaundo = false, over = false;
     if (srow) {
         same = !wave_rows_differ(d, d.dense + (size_t)e.y * d.NP, srow, nullptr, nullptr);
-    } else if (phase != 2 && !(e.w & 0x80000000u) && d.ulog && sender >= d.lo && sender < d.lo + d.NL) {
+    } else if (phase != 2 && !(e.w & 0x80000000u) && d.ulog && !(dt & 4u) && sender >= d.lo && sender < d.lo + d.NL) {
         // the sender was clean at issue (C_o = e.z) and has changed since only by this phase's merges: its issue-time
-        // row is its row with the logged words restored
+        // row is its row with the logged words restored (a sender that received nothing this phase has an empty log:
+        // run_waves clears every row's count before k_recv)
         const uint32_t sl = sender - d.lo, nlog = d.ulog_cnt[sl];
-        if (nlog <= ULOG_CAP) {
+        over = nlog > d.ulog_cap;
+        if (!over) {
             bool done = false;
             const bool differ = wave_rows_differ_undo(d, d.dense + (size_t)e.y * d.NP, d.mw + (size_t)sl * d.NP,
                                                       d.ulog + (size_t)sl * ULOG_CAP, nlog, done);
@@ -1713,7 +1720,10 @@ __global__ void k_defer_eq(DS d, const uint4 *defer, const uint32_t *defer_cnt, 
         eq[i] = same ? 1 : 0;
         ctr_add(d, C_X_DEFER, 1ull);
         if (same) ctr_add(d, viarep ? C_X_DEFER_REP : viaundo ? C_X_DEFER_UNDO : C_X_DEFER_EQ, 1ull);
+        else if (viarep || viaundo) ctr_add(d, viarep ? C_X_DEFER_REP_DIFF : C_X_DEFER_UNDO_DIFF, 1ull);
         if (!srow && !viaundo) ctr_add(d, C_X_DEFER_NOROW, 1ull);
+        if (over) ctr_add(d, C_X_DEFER_UNDO_OVER, 1ull);
+        if (!(e.w & 0x80000000u)) ctr_add(d, C_X_DEFER_CLEAN, 1ull);
     }
 }
 
@@ -1737,6 +1747,7 @@ __global__ void k_recv_finish(DS d, const uint4 *defer, const uint32_t *defer_cn
     if (differ) {
         resp.kind = 1; resp.off_lo = slot; resp.len = d.dense_meta[slot].z;
         ctr_add(d, phase == 1 ? C_FULL_SYNCS_PINGREQ : C_FULL_SYNCS, 1ull);
+        ctr_add(d, C_X_DEFER_FS, 1ull);
         if (phase == 2) {
             const uint32_t ol = d.dense_meta[slot].x - d.lo;
             if (d.njobs[ol] < d.maxjobs) d.jobs[(size_t)ol * d.maxjobs + d.njobs[ol]++] = pair;

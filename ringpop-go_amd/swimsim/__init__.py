@@ -57,7 +57,7 @@ class Tuning(C.Structure):
     """swimsim_tuning (include/swimsim.h): engine variants for tests and diagnostics, -1 = the production default."""
     _fields_ = [("hot_slots", C.c_int32), ("dense_slots", C.c_int32), ("cs_async", C.c_int32),
                 ("cs_async_rows", C.c_int32), ("cs_narrow_rows", C.c_int32), ("cs_ref", C.c_int32),
-                ("fault_inject", C.c_int32)]
+                ("fault_inject", C.c_int32), ("defer_test", C.c_int32)]
 
 
 def make_tuning(tuning):
@@ -540,11 +540,13 @@ class Cluster:
     def kernel_units(self):
         """unit counts behind kernel_times' bytes since enable_timing: rows hashed per checksum kernel, changes
         processed / applied per merge kernel, records issued, ..."""
-        cap = 32
+        cap = 64
         names = (C.c_char_p * cap)()
         vals = np.zeros(cap, np.float64)
         n = C.c_size_t()
         self._chk(load_library().swimsim_kernel_units(self.h, names, vals.ctypes.data, cap, C.byref(n)))
+        if n.value > cap:
+            raise SwimsimError(f"swimsim_kernel_units has {n.value} names, the binding reads {cap}")
         return {names[i].decode(): float(vals[i]) for i in range(n.value)}
 
     def profile_mark(self, mark_id):

@@ -9,6 +9,8 @@ oracle at every chunk boundary, bit-exact. They also check that the side-stream 
 synchronous path (swimsim_tuning.cs_async = 0) give identical states.
 """
 
+from contextlib import closing
+
 import numpy as np
 import pytest
 
@@ -94,16 +96,17 @@ def test_chunked_sharded_self_only():
 
 def test_async_equals_sync_path():
     wl = W.config3(n=1024, rounds=50, kill_round=5)
-    sync = swimsim.Cluster(wl.n, tuning={"cs_async": 0})
-    asy = swimsim.Cluster(wl.n, tuning={"cs_async": 1})
-    for r0 in range(0, wl.rounds, 10):
-        ev = [e for e in wl.events if r0 <= e[0] < r0 + 10]
-        sync.step(10, ev)
-        asy.step(10, ev)
-        assert (sync.checksums() == asy.checksums()).all(), f"checksums differ after round {r0 + 10}"
-        assert sync.digest() == asy.digest(), f"state differs after round {r0 + 10}"
-    assert sync.counters() == asy.counters()
-    assert np.array_equal(sync.rows()[0], asy.rows()[0])
+    # (both handles are closed also when an assert fails)
+    with closing(swimsim.Cluster(wl.n, tuning={"cs_async": 0})) as sync, \
+            closing(swimsim.Cluster(wl.n, tuning={"cs_async": 1})) as asy:
+        for r0 in range(0, wl.rounds, 10):
+            ev = [e for e in wl.events if r0 <= e[0] < r0 + 10]
+            sync.step(10, ev)
+            asy.step(10, ev)
+            assert (sync.checksums() == asy.checksums()).all(), f"checksums differ after round {r0 + 10}"
+            assert sync.digest() == asy.digest(), f"state differs after round {r0 + 10}"
+        assert sync.counters() == asy.counters()
+        assert np.array_equal(sync.rows()[0], asy.rows()[0])
 
 
 def test_side_stream_reference_row_path_vs_oracle():
@@ -124,19 +127,19 @@ def test_side_stream_reference_row_path_equals_narrow_kernel():
     it (128: side launches keep the narrow kernel) gives identical checksums, state digests and counters at every chunk
     boundary."""
     wl = W.config3(n=16384, rounds=30, kill_round=5)
-    a = swimsim.Cluster(wl.n, tuning={"fault_inject": 256})
-    b = swimsim.Cluster(wl.n, tuning={"fault_inject": 128})
-    for r0 in range(0, wl.rounds, 5):
-        ev = [e for e in wl.events if r0 <= e[0] < r0 + 5]
-        a.step(5, ev)
-        b.step(5, ev)
-        bad = np.nonzero(a.checksums() != b.checksums())[0]
-        assert len(bad) == 0, f"after round {r0 + 5}: {len(bad)} checksums differ, first {bad[:5]}"
-        assert a.digest() == b.digest()
-    assert a.counters() == b.counters()
-    sa, sb = a.checksum_path_stats(), b.checksum_path_stats()
-    print("side set", sa, "none", sb)
-    assert sa["delta_launches"] > sb["delta_launches"], (sa, sb)
+    with closing(swimsim.Cluster(wl.n, tuning={"fault_inject": 256})) as a, \
+            closing(swimsim.Cluster(wl.n, tuning={"fault_inject": 128})) as b:
+        for r0 in range(0, wl.rounds, 5):
+            ev = [e for e in wl.events if r0 <= e[0] < r0 + 5]
+            a.step(5, ev)
+            b.step(5, ev)
+            bad = np.nonzero(a.checksums() != b.checksums())[0]
+            assert len(bad) == 0, f"after round {r0 + 5}: {len(bad)} checksums differ, first {bad[:5]}"
+            assert a.digest() == b.digest()
+        assert a.counters() == b.counters()
+        sa, sb = a.checksum_path_stats(), b.checksum_path_stats()
+        print("side set", sa, "none", sb)
+        assert sa["delta_launches"] > sb["delta_launches"], (sa, sb)
 
 
 @pytest.mark.parametrize("tuning", [{"fault_inject": 1024}, {}])

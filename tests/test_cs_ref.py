@@ -9,6 +9,8 @@ shift ranges, workgroups whose window does not fit fall back), incarnation burst
 differ from the reference almost everywhere). At size, the path is compared with the engine's own checksums on real
 cascade rows (swimsim_bench_checksum mode 5).
 """
+from contextlib import closing
+
 import numpy as np
 import pytest
 
@@ -79,15 +81,15 @@ def test_selfstart_n1024_every_round():
 @pytest.mark.parametrize("n,rounds", [(4096, 18), (16384, 16)])
 def test_mode5_on_real_cascade_rows(n, rounds):
     wl = W.config3(n=n, rounds=rounds + 1, kill_round=10)
-    c = swimsim.Cluster(n)
-    for r in range(rounds):
-        c.step(1, wl.events_for(r))
-    ref = c.checksums().copy()
-    for rows in (1024, 3000, n):
-        c.bench_checksum(rows, 5, reps=1)
-        got = c.checksums()
-        assert (got[:rows] == ref[:rows]).all(), f"{rows} rows: {(got[:rows] != ref[:rows]).sum()} differ"
-    print(f"real rows n{n}", c.checksum_path_stats())
+    with closing(swimsim.Cluster(n)) as c:                         # (closed also when an assert fails: at-size handles
+        for r in range(rounds):                                    # left open make the next tests fail with ENOMEM)
+            c.step(1, wl.events_for(r))
+        ref = c.checksums().copy()
+        for rows in (1024, 3000, n):
+            c.bench_checksum(rows, 5, reps=1)
+            got = c.checksums()
+            assert (got[:rows] == ref[:rows]).all(), f"{rows} rows: {(got[:rows] != ref[:rows]).sum()} differ"
+        print(f"real rows n{n}", c.checksum_path_stats())
 
 
 def test_stager_priority_schedule_on_real_cascade_rows():
@@ -98,18 +100,18 @@ def test_stager_priority_schedule_on_real_cascade_rows():
     The path's checksums must equal the production kernels' (swimsim_bench_checksum mode 0) on every row."""
     n = 32768
     wl = W.config3(n=n, rounds=21, kill_round=10)
-    c = swimsim.Cluster(n, tuning={"fault_inject": 16})
-    for r in range(20):
-        c.step(1, wl.events_for(r))
-        if r in (15, 17, 19):
-            c.bench_checksum(n, 0, reps=1)
-            ref = c.checksums().copy()
-            for rep in range(2):
-                c.bench_checksum(n, 5, reps=1)
-                got = c.checksums()
-                bad = np.nonzero(got != ref)[0]
-                assert len(bad) == 0, f"round {r} rep {rep}: {len(bad)} rows differ, first {bad[:5]}"
-    print("stager priority", c.checksum_path_stats())
+    with closing(swimsim.Cluster(n, tuning={"fault_inject": 16})) as c:
+        for r in range(20):
+            c.step(1, wl.events_for(r))
+            if r in (15, 17, 19):
+                c.bench_checksum(n, 0, reps=1)
+                ref = c.checksums().copy()
+                for rep in range(2):
+                    c.bench_checksum(n, 5, reps=1)
+                    got = c.checksums()
+                    bad = np.nonzero(got != ref)[0]
+                    assert len(bad) == 0, f"round {r} rep {rep}: {len(bad)} rows differ, first {bad[:5]}"
+        print("stager priority", c.checksum_path_stats())
 
 
 def test_csr_alloc_failure_leaves_production_kernels_in_charge():
@@ -203,17 +205,17 @@ def test_perturbed_handover_on_real_cascade_rows(roles, seed):
     chain wave (-DC3_T_SHAREDDONE, round 5's race) fails this test."""
     n = 32768
     wl = W.config3(n=n, rounds=21, kill_round=10)
-    c = swimsim.Cluster(n, tuning={"fault_inject": 64 | (roles << 8) | (seed << 12)})
-    for r in range(20):
-        c.step(1, wl.events_for(r))
-        if r in (15, 18):
-            c.bench_checksum(n, 0, reps=1)
-            ref = c.checksums().copy()
-            c.bench_checksum(n, 5, reps=1)
-            got = c.checksums()
-            bad = np.nonzero(got != ref)[0]
-            assert len(bad) == 0, f"roles {roles} round {r}: {len(bad)} rows differ, first {bad[:5]}"
-    print("perturbed hand-over", roles, c.checksum_path_stats())
+    with closing(swimsim.Cluster(n, tuning={"fault_inject": 64 | (roles << 8) | (seed << 12)})) as c:
+        for r in range(20):
+            c.step(1, wl.events_for(r))
+            if r in (15, 18):
+                c.bench_checksum(n, 0, reps=1)
+                ref = c.checksums().copy()
+                c.bench_checksum(n, 5, reps=1)
+                got = c.checksums()
+                bad = np.nonzero(got != ref)[0]
+                assert len(bad) == 0, f"roles {roles} round {r}: {len(bad)} rows differ, first {bad[:5]}"
+        print("perturbed hand-over", roles, c.checksum_path_stats())
 
 
 def test_colx_rebuild_after_raw_writes_every_round():
@@ -245,12 +247,12 @@ def test_side_stream_path_on_real_cascade_rows():
     wave: every checksum equals the engine's own (memberlist.go:83-128)."""
     n = 16384
     wl = W.config3(n=n, rounds=17, kill_round=10)
-    c = swimsim.Cluster(n)
-    for r in range(16):
-        c.step(1, wl.events_for(r))
-    ref = c.checksums().copy()
-    for rows in (8192, 12288):
-        ms = c.bench_checksum(rows, 6, reps=1)
-        got = c.checksums()
-        assert (got[:rows] == ref[:rows]).all(), f"{rows} rows: {(got[:rows] != ref[:rows]).sum()} differ"
-        print(f"side-stream path, {rows} rows: {ms:.2f} ms")
+    with closing(swimsim.Cluster(n)) as c:
+        for r in range(16):
+            c.step(1, wl.events_for(r))
+        ref = c.checksums().copy()
+        for rows in (8192, 12288):
+            ms = c.bench_checksum(rows, 6, reps=1)
+            got = c.checksums()
+            assert (got[:rows] == ref[:rows]).all(), f"{rows} rows: {(got[:rows] != ref[:rows]).sum()} differ"
+            print(f"side-stream path, {rows} rows: {ms:.2f} ms")
