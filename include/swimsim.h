@@ -95,7 +95,8 @@ typedef struct swimsim_tuning {
     int32_t defer_test;       /* tests only (ABI 6): which ways a deferred full-sync decision may be settled without a hash
                                  (DESIGN.md §5), bits: 1 = a still-clean sender's current row is not compared directly;
                                  2 = no checksum representatives; 4 = no undo log; 8 = the undo log holds 2 entries per
-                                 row instead of 64; 16 = the representative table has one slot (every checksum
+                                 row instead of 1,024 (a pending-live sender's receive wave then rebuilds its issue-time
+                                 row once it has logged more); 16 = the representative table has one slot (every checksum
                                  collides, the last store wins, the losing decisions fall through). Results are
                                  identical with every combination; <= 0 (default, and the 0 an older caller's
                                  zero-initialised struct reads): the production engine */

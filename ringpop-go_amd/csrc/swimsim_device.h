@@ -50,7 +50,11 @@ enum Counter {
     // the "differ" side of the two shortcuts (the comparison ran and found the rows different: the decision hashes),
     // deferred decisions that ended as a full sync (k_recv_finish), undo branches that met a log past its cap, and
     // decisions whose sender's C_o was known at issue (every one that is not a pending sender's)
-    C_X_DEFER_REP_DIFF, C_X_DEFER_UNDO_DIFF, C_X_DEFER_FS, C_X_DEFER_UNDO_OVER, C_X_DEFER_CLEAN, C_NALL
+    C_X_DEFER_REP_DIFF, C_X_DEFER_UNDO_DIFF, C_X_DEFER_FS, C_X_DEFER_UNDO_OVER, C_X_DEFER_CLEAN,
+    // dense row copies k_issue made for dirty senders (none since the pending-live state), and the
+    // issue-time rows rebuilt instead: by a receive wave before the content would be lost (late), and at resolution
+    // time for a decision that needs the sender's checksum (mat)
+    C_X_ISSUE_SNAPS, C_X_LAZY_LATE, C_X_LAZY_MAT, C_NALL
 };
 
 constexpr int CTR_SHARDS = 64, CTR_STRIDE = 64;   // d.ctr is [CTR_SHARDS][CTR_STRIDE] u64
@@ -156,17 +160,29 @@ struct DS {
     // the colx columns without a hot slot (ucnt[1], any order). Rows are equal iff equal at the hot slots and ucold.
     uint32_t *ucl, *uhk, *ucold, *ucnt;
     // the words a receive phase's merges overwrote (k_recv, phases D and Q2): per row up to ulog_cap {member, old word}
-    // in apply order and their count (ulog_cap + 1: more, not usable; 0 for every row when the phase starts, so a row
-    // that receives nothing has an empty log). A row that was clean when it issued its message and changed only in the
-    // phase since is its issue-time row with the first old word of each logged member restored (k_defer_eq, DESIGN.md
-    // §5); nullptr: off
+    // in apply order (stored up to ulog_stride: a pending-live row's wave looks at its count between two batches of
+    // 64 * 4 changes) and their count (ulog_cap + 1: more, not usable; 0 for every row when the phase starts, so a row
+    // that receives nothing has an empty log). A row that changed only in the phase since it issued its message is its
+    // issue-time row with the first old word of each logged member restored (k_defer_eq, wave_rebuild_issue_row,
+    // DESIGN.md §5); nullptr: off
     uint2 *ulog;
     uint32_t *ulog_cnt;
     uint32_t ulog_cap;        // entries a row's log may hold: ULOG_CAP (tests: 2, swimsim_tuning.defer_test bit 8)
+    uint32_t ulog_stride;     // storage stride of a row's log (ULOG_STRIDE, set at create): ulog_cap + one merge batch
     uint32_t defer_test;      // swimsim_tuning.defer_test (tests: which ways k_defer_eq may settle a decision); 0
+    // a sender that was dirty when it issued (sS[o] = SRC_PEND, "pending, live") has no snapshot: what hashing its
+    // issue-time row needs beside the words, the checksum string's length and last included member at issue
+    uint32_t *ilen;           // [NL]
+    int32_t *ilast;           // [NL]
 };
-constexpr uint32_t ULOG_CAP = 64;   // storage stride of a row's log, and the most ulog_cap can be: k_defer_eq holds a
-                                    // log in one wave's lanes
+// entries of a row's undo log. A row of the 65,536-member cascade applies at most about 655 changes in a receive phase
+// (one per killed member), so no log of the flagship workload overflows; 10 KB per row beside the row's 1.3 MB. The
+// storage holds one merge batch (64 lanes x MB = 4 changes) more than the capacity: wave_merge_body
+constexpr uint32_t ULOG_CAP = 1024, ULOG_STRIDE = ULOG_CAP + 256;
+// sS[o] / sS2[o] of a local sender: SRC_NONE = C_o known (sC[o]), a dense slot = its issue-time snapshot, SRC_PEND =
+// dirty at issue and not copied (the row is rebuilt on demand), SRC_CLAIM = being rebuilt at resolution time
+// (k_lazy_mat). Both stay below bit 31, which marks a remote sender's slot in a deferred decision.
+constexpr uint32_t SRC_PEND = 0x7FFFFFFEu, SRC_CLAIM = 0x7FFFFFFDu;
 
 // hot slot of member m, SRC_NONE when m has none (or hot columns are off)
 __device__ __forceinline__ uint32_t hot_slot(const DS &d, uint32_t m) { return d.hidx ? d.hidx[m] : SRC_NONE; }

@@ -1240,6 +1240,10 @@ int bound_lazy_snapshots(swimsim *h, int mode) {
 // shard about). Sharded phases D and Q2 are collective: two exchanges carry the requests and answers.
 int resolve_deferred(swimsim *h, int phase, MsgDesc *rdesc, uint32_t maxn) {
     const bool remote = h->G > 1 && phase != 2;
+    // the phase's lazy-slot array: the pending-live senders' state is read from it now (k_recv may have published a
+    // rebuilt row), and k_lazy_mat publishes the rows rebuilt here; none in the heal ping's resolution
+    uint32_t *sS = phase == 0 ? h->sS : phase == 1 ? h->sS2 : nullptr;
+    const uint32_t *sI = phase == 1 ? h->sI2 : h->sI;
     // k_recv_finish and k_x_csresp read checksums the side stream may still be computing (clean
     // receivers and pending senders refer to side slots): wait for it unless nothing was deferred
     if (remote || phase == 2)
@@ -1255,17 +1259,22 @@ int resolve_deferred(swimsim *h, int phase, MsgDesc *rdesc, uint32_t maxn) {
                                h->rep_mask, h->rep_gen);
         }
         hipLaunchKernelGGL(k_defer_eq, dim3(blocks_for_waves(maxn)), dim3(SWIM_WAVE_BLOCK), 0, h->s, h->d, h->defer, h->defer_cnt,
-                           phase, h->defer_eq, h->rep_tab, h->rep_mask, h->rep_gen);
+                           phase, h->defer_eq, h->rep_tab, h->rep_mask, h->rep_gen, sS);
+        if (sS)                                                    // (exits at once when nothing was deferred)
+            hipLaunchKernelGGL(k_lazy_mat, dim3(blocks_for_waves(maxn)), dim3(SWIM_WAVE_BLOCK), 0, h->s, h->d, h->defer,
+                               h->defer_eq, (const uint4 *)nullptr, h->defer_cnt, 0xFFFFFFFFu, phase, sS, sI);
         hipLaunchKernelGGL(k_defer_ids, dim3(blocks_for_threads(maxn)), dim3(256), 0, h->s, h->d, h->defer,
-                           h->defer_cnt, h->defer_eq, h->list, h->cnt);
+                           h->defer_cnt, h->defer_eq, h->list, h->cnt, phase, sS);
     }
     if (remote) {
         HIPCHK(h, hipMemsetAsync(h->csreqcnt, 0, 4, h->s));
         hipLaunchKernelGGL(k_x_csreq, dim3(blocks_for_threads(maxn)), dim3(256), 0, h->s, h->d, h->defer, h->defer_cnt,
                            phase, h->xitems, h->xcnt, h->xcap);
         if (int rc = xchg(h)) return rc;
+        hipLaunchKernelGGL(k_lazy_mat, dim3(blocks_for_waves(h->keycap)), dim3(SWIM_WAVE_BLOCK), 0, h->s, h->d,
+                           (const uint4 *)nullptr, (const uint8_t *)nullptr, h->csreq, h->csreqcnt, h->keycap, phase, sS, sI);
         hipLaunchKernelGGL(k_csreq_ids, dim3(blocks_for_threads(h->keycap)), dim3(256), 0, h->s, h->d, h->csreq,
-                           h->csreqcnt, h->list, h->cnt);
+                           h->csreqcnt, h->list, h->cnt, sS);
         maxlist += h->keycap;
     }
     {
@@ -1282,12 +1291,12 @@ int resolve_deferred(swimsim *h, int phase, MsgDesc *rdesc, uint32_t maxn) {
     }
     if (remote) {
         hipLaunchKernelGGL(k_x_csresp, dim3(blocks_for_threads(h->keycap)), dim3(256), 0, h->s, h->d, h->csreq,
-                           h->csreqcnt, h->xitems, h->xcnt, h->xcap);
+                           h->csreqcnt, h->xitems, h->xcnt, h->xcap, sS);
         if (int rc = xchg(h)) return rc;
     }
     Scope sc(h, phase == 1 ? F_PINGREQ : F_RECVFIN);
     hipLaunchKernelGGL(k_recv_finish, dim3(blocks_for_threads(maxn)), dim3(256), 0, h->s, h->d, h->defer,
-                       h->defer_cnt, rdesc, phase, h->fsflag, h->rcs, h->defer_eq);
+                       h->defer_cnt, rdesc, phase, h->fsflag, h->rcs, h->defer_eq, sS);
     return 0;
 }
 
@@ -1958,8 +1967,10 @@ int swimsim_create(const swimsim_config *cfg, swimsim_t **out) {
         (rc = dalloc(h, &h->defer_eq, KC + 2 * (size_t)h->NL + 64, "defer eq")) ||
         (rc = dalloc(h, &h->rep_tab, (size_t)rep_slots(h->NL), "checksum representatives")) ||
         (rc = dalloc(h, &h->fp_tab, (size_t)rep_slots(h->NL) * 4, "dedup groups")) ||
-        (rc = dalloc(h, &h->d.ulog, (size_t)h->NL * ULOG_CAP, "receive-phase undo log")) ||
+        (rc = dalloc(h, &h->d.ulog, (size_t)h->NL * ULOG_STRIDE, "receive-phase undo log")) ||
         (rc = dalloc(h, &h->d.ulog_cnt, (size_t)h->NL, "receive-phase undo log counts")) ||
+        (rc = dalloc(h, &h->d.ilen, (size_t)h->NL, "issue-time checksum lengths")) ||
+        (rc = dalloc(h, &h->d.ilast, (size_t)h->NL, "issue-time last members")) ||
         (rc = dalloc(h, &h->defer_cnt, 1, "defer_cnt")) || (rc = dalloc(h, &h->exh_list, h->NL, "exh_list")) ||
         (rc = dalloc(h, &h->exh_cnt, 1, "exh_cnt")) || (rc = dalloc(h, &h->scratch, (size_t)64 * (h->NP / 32), "scratch")) ||
         (rc = dalloc(h, &h->need, h->N, "need")) || (rc = dalloc(h, &h->digest_buf, 4, "digest")) ||
@@ -1967,7 +1978,8 @@ int swimsim_create(const swimsim_config *cfg, swimsim_t **out) {
         (rc = dalloc(h, &h->npairs, 1, "npairs")))
         return bail(rc);
     h->rep_mask = (h->defer_test & 16) ? 0u : rep_slots(h->NL) - 1u;   // (tests: one slot, every checksum collides)
-    h->d.ulog_cap = (h->defer_test & 8) ? 2u : ULOG_CAP;               // (tests: logs past the cap at small sizes)
+    h->d.ulog_stride = ULOG_STRIDE;
+    h->d.ulog_cap = (h->defer_test & 8) ? 2u : ULOG_CAP;            // (tests: logs past the cap at small sizes)
     h->d.defer_test = (uint32_t)h->defer_test;
     hipMemset(h->rep_tab, 0, (size_t)rep_slots(h->NL) * 8);      // (generation 0: every entry empty)
     h->evcap = 4 * h->N + 64;
@@ -2829,12 +2841,13 @@ int swimsim_kernel_units(swimsim_t *h, const char **names, double *values, size_
                                "hot_slots", "diag_stamp4", "diag_stamp5", "diag_stamp6", "diag_stamp7",
                                "dense_resp", "dense_jobs", "jobs_applied", "dense_heal", "defer", "defer_eq", "defer_norow",
                                "defer_rep", "defer_undo", "defer_rep_diff", "defer_undo_diff", "defer_fs",
-                               "defer_undo_over", "defer_clean"};
+                               "defer_undo_over", "defer_clean", "issue_snaps", "lazy_late", "lazy_mat"};
     const int ki[] = {C_X_CS_ROWS, C_X_CS_ROWS_N, C_X_CS_DUP, C_X_MERGED, C_X_APPLIED, C_X_RISSUED, C_X_RCALLS,
                       C_X_MERGED_R, C_X_APPLIED_R, C_X_BUMPED, C_X_ISSUED, -1, C_NALL, C_NALL + 1, C_NALL + 2, C_NALL + 3,
                       -2, C_NALL + 4, C_NALL + 5, C_NALL + 6, C_NALL + 7, C_X_DENSE_RESP, C_X_DENSE_JOBS, C_X_JOBS_APPLIED,
                       C_X_DENSE_HEAL, C_X_DEFER, C_X_DEFER_EQ, C_X_DEFER_NOROW, C_X_DEFER_REP, C_X_DEFER_UNDO,
-                      C_X_DEFER_REP_DIFF, C_X_DEFER_UNDO_DIFF, C_X_DEFER_FS, C_X_DEFER_UNDO_OVER, C_X_DEFER_CLEAN};
+                      C_X_DEFER_REP_DIFF, C_X_DEFER_UNDO_DIFF, C_X_DEFER_FS, C_X_DEFER_UNDO_OVER, C_X_DEFER_CLEAN,
+                      C_X_ISSUE_SNAPS, C_X_LAZY_LATE, C_X_LAZY_MAT};
     static_assert(sizeof(kn) / sizeof(kn[0]) == sizeof(ki) / sizeof(ki[0]), "one counter per name");
     uint32_t hot = 0;                                              // hot slots in use now (not a delta)
     if (h->d.hot_cnt) {

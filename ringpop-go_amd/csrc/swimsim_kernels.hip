@@ -320,6 +320,77 @@ __device__ __forceinline__ void wave_copy16(uint4 *dst, const uint4 *src, uint32
     }
 }
 
+// The issue-time row of a pending-live sender (k_issue, sS[o] = SRC_PEND) as a dense snapshot, built by one wave: the
+// live row, then the words the phase's merges overwrote put back newest first, so that the first logged word of a
+// member, its issue-time word, is the last one stored (nlog entries of log, all of them stored: at most ulog_stride).
+// The stores of one step go to distinct members (within a chunk of 64 log entries only the first entry of a member
+// stores), and the steps are fenced apart. self_e, len, last: the row's own incarnation, checksum-string length and
+// last included member at issue. Returns the slot (SRC_NONE: the pool is full, E_DENSE).
+// (Out of line, with the few fields it needs passed one by one: inlined into k_recv's merge loop it raised that kernel's
+// scratch from 84 to 832 B per lane, and a callee that takes the DS block by reference makes every launch copy it to
+// scratch. It runs on cold paths only.)
+__device__ __noinline__ uint32_t wave_rebuild_impl(const uint32_t *src, uint32_t *dense, uint32_t NP, uint32_t N,
+                                                   uint32_t *dense_cur, uint32_t dense_cap, uint32_t *err, uint4 *dense_meta,
+                                                   uint32_t *dense_len, int32_t *dense_last, const uint2 *log, uint32_t nlog,
+                                                   uint32_t o, uint32_t self_e, uint32_t len, int32_t last) {
+    uint32_t slot = 0;
+    if (lane_id() == 0) slot = atomicAdd(dense_cur, 1u);
+    slot = (uint32_t)__builtin_amdgcn_readlane((int)slot, 0);
+    if (slot >= dense_cap) {
+        if (lane_id() == 0) atomicOr(err, E_DENSE);
+        return SRC_NONE;
+    }
+    __threadfence_block();                                         // (the wave's own row stores so far)
+    uint32_t *dst = dense + (size_t)slot * NP;
+    wave_copy16((uint4 *)dst, (const uint4 *)src, NP / 4);
+    __threadfence_block();
+    for (int c0 = nlog ? (int)((nlog - 1u) & ~63u) : -1; c0 >= 0; c0 -= 64) {
+        const uint32_t k = (uint32_t)c0 + lane_id();
+        const uint2 L = k < nlog ? log[k] : make_uint2(0xFFFFFFFFu, 0u);
+        bool first = k < nlog;
+        for (int j = 0; j < 63; j++) {
+            const uint32_t lm = (uint32_t)__builtin_amdgcn_readlane((int)L.x, j);
+            first = first && !((uint32_t)j < lane_id() && lm == L.x);
+        }
+        if (first) dst[L.x] = L.y;
+        __threadfence_block();
+    }
+    int known = 0;
+    for (uint32_t m = lane_id(); m < N; m += 64) known += (dst[m] & 7u) != ST_UNKNOWN;
+    known = wsum(known);
+    if (lane_id() == 0) {
+        dense_meta[slot] = make_uint4(o, self_e, (uint32_t)known, 0);
+        dense_len[slot] = len;
+        dense_last[slot] = last;
+    }
+    return slot;
+}
+__device__ __forceinline__ uint32_t wave_rebuild_issue_row(const DS &d, uint32_t ol, uint32_t o, uint32_t self_e,
+                                                           uint32_t nlog) {
+    return wave_rebuild_impl(d.mw + (size_t)ol * d.NP, d.dense, d.NP, d.N, d.dense_cur, d.dense_cap, d.err, d.dense_meta,
+                             d.dense_len, d.dense_last, d.ulog + (size_t)ol * d.ulog_stride, nlog, o, self_e, d.ilen[ol],
+                             d.ilast[ol]);
+}
+static_assert(ULOG_STRIDE >= ULOG_CAP + 64 * MB, "the log's storage holds one merge batch beyond its capacity");
+// a receive wave's view of its own row as a sender of the phase (k_recv): pend = the row is pending, live; sS / sI = the
+// phase's lazy-slot and issue-time incarnation arrays
+struct LazyCtx {
+    uint32_t *sS;
+    const uint32_t *sI;
+    bool pend;
+};
+// the receive wave of a pending-live row is about to lose issue-time content (its log has passed its capacity and is
+// within a batch of the end of its storage, or a dense message is merged): the issue-time row is rebuilt now and
+// published in sS[o]
+__device__ __forceinline__ void wave_lazy_late(const DS &d, uint32_t ol, uint32_t o, LazyCtx &lz, uint32_t nlog) {
+    const uint32_t slot = wave_rebuild_issue_row(d, ol, o, lz.sI[o], nlog);
+    lz.pend = false;
+    if (lane_id() == 0) {
+        if (slot != SRC_NONE) lz.sS[o] = slot;
+        ctr_add(d, C_X_LAZY_LATE, 1ull);
+    }
+}
+
 // a dense message (MembershipAsChanges: full sync, reverse full sync, heal) streams the whole row. (Kept
 // inline: an out-of-line call makes every launch copy the DS argument block to scratch, 480 B per lane.)
 __device__ __forceinline__ void wave_merge_dense(const DS &d, uint32_t ol, uint32_t o, const MsgDesc &md,
@@ -356,10 +427,10 @@ __device__ __forceinline__ void merge_first(const DS &d, const MsgDesc &md, uint
     }
 }
 // (dctr >= 0: the measurement counter a dense message adds one to; pre0: the first batch from merge_first, or null;
-// ulog: the receive phase's undo log position of this row (k_recv), or null)
+// ulog: the receive phase's undo log position of this row (k_recv), or null; lz: the row as a sender of the phase, k_recv)
 __device__ __forceinline__ void wave_merge_body(const DS &d, uint32_t ol, uint32_t o, const MsgDesc &md, uint32_t now_e,
                                                 uint32_t sched_r, MAcc &acc, int dctr, const uint4 *pre0 = nullptr,
-                                                uint32_t *ulog = nullptr) {
+                                                uint32_t *ulog = nullptr, LazyCtx *lz = nullptr) {
     const uint32_t *rowp = d.mw + (size_t)ol * d.NP;
     const uint32_t *hrow = d.hmw + (size_t)ol * d.HP;
     if (md.kind == 0) {
@@ -389,12 +460,18 @@ __device__ __forceinline__ void wave_merge_body(const DS &d, uint32_t ol, uint32
                     const bool ap = acc.napp != before;
                     const unsigned long long b = __ballot(ap);
                     const uint32_t at = *ulog + (uint32_t)__popcll(b & lanemask_lt());
-                    if (ap && at < d.ulog_cap) d.ulog[(size_t)ol * ULOG_CAP + at] = make_uint2(rec_m(rec[u]), cur[u]);
+                    if (ap && at < d.ulog_stride) d.ulog[(size_t)ol * d.ulog_stride + at] = make_uint2(rec_m(rec[u]), cur[u]);
                     *ulog += (uint32_t)__popcll(b);
                 }
             }
+            // A pending-live row whose log has passed its capacity: the storage keeps one batch (64 * MB entries) beyond
+            // the capacity, so every word overwritten so far is in the log, and the row is rebuilt from it here, between
+            // two batches, outside the merge steps. (Overflow is seen on the changes that did apply: a bound on md.len
+            // would rebuild the row of nearly every sender of the faulty wave, whose long messages apply next to nothing.)
+            if (ulog && lz && lz->pend && *ulog > d.ulog_cap) wave_lazy_late(d, ol, o, *lz, *ulog);
         }
     } else if (md.kind == 1) {
+        if (ulog && lz && lz->pend) wave_lazy_late(d, ol, o, *lz, *ulog);
         wave_merge_dense(d, ol, o, md, now_e, sched_r, acc);
         if (dctr >= 0 && lane_id() == 0) ctr_add(d, dctr, 1ull);
         if (ulog) *ulog = d.ulog_cap + 1u;                          // (not logged: the row's issue-time words are lost)
@@ -413,10 +490,11 @@ __device__ void wave_merge_msg(const DS &d, uint32_t ol, uint32_t o, const MsgDe
 // the same on a wave's register copy of the row scalars (RowPre)
 __device__ __forceinline__ void wave_merge_msg_pre(const DS &d, uint32_t ol, uint32_t o, const MsgDesc &md, uint32_t now_e,
                                                    uint32_t sched_r, int cset, RowPre &p, int dctr = -1,
-                                                   const uint4 *pre0 = nullptr, bool logit = false) {
+                                                   const uint4 *pre0 = nullptr, bool logit = false,
+                                                   LazyCtx *lz = nullptr) {
     MAcc acc;
     acc.tag = p.useq;
-    wave_merge_body(d, ol, o, md, now_e, sched_r, acc, dctr, pre0, logit && d.ulog ? &p.ulog : nullptr);
+    wave_merge_body(d, ol, o, md, now_e, sched_r, acc, dctr, pre0, logit && d.ulog ? &p.ulog : nullptr, lz);
     wave_finalize_pre(d, ol, acc, cset, p);
 }
 
@@ -787,7 +865,7 @@ __device__ bool wave_snapshot(const DS &d, uint32_t ol, uint32_t o, MsgDesc &out
     uint4 *dst = (uint4 *)(d.dense + (size_t)slot * d.NP);
     int known = 0;
     // (SNAP_MB loads in flight per lane: one at a time, each copy iteration waited for its load, 256 HBM round trips for
-    // a 256-KB row, and the snapshotting senders' waves set k_issue's time: 0.4 ms a launch)
+    // a 256-KB row. k_issue no longer copies the dirty senders' rows at all: DESIGN.md §5, pending-live senders)
     const uint32_t n4 = d.NP / 4;
     for (uint32_t i = lane_id(); i < n4; i += 64 * SNAP_MB) {
         uint4 v[SNAP_MB];
@@ -1209,24 +1287,36 @@ __global__ void k_list_one(uint32_t *list, uint32_t *cnt, uint32_t ol, const DS 
 }
 
 // phase I (ping_sender.go:43-66) / Q1: snapshot S_o, C_o, I_o for the senders of this phase
-// Lazy C_o (sS != nullptr): a dirty sender's checksum is not computed here. Its row is snapshotted
-// (sS[o] = dense slot) and hashed only if a receiver compares it (IssueAsReceiver with nothing left to
-// send, disseminator.go:170-180), in the batched deferred resolution after the receive waves.
+// Lazy C_o (sS != nullptr): a dirty sender's checksum is not computed here, and its row is not copied
+// either: it is marked pending, live (sS[o] = SRC_PEND). A receiver that compares it (IssueAsReceiver with
+// nothing left to send, disseminator.go:170-180) defers, and the batched resolution after the receive waves
+// compares against the live row with the phase's undo log undone, or rebuilds and hashes the issue-time row.
 __global__ void k_issue(DS d, int mode, const int32_t *tgt, const uint8_t *failed, MsgDesc *sdesc, uint32_t *sI,
                         uint32_t *sC, uint32_t *sS) {
     const uint32_t ol = wave_gid();
     if (ol >= d.NL) return;
-    if (mode == 0 && tgt[ol] < 0) return;
-    if (mode == 1 && !failed[ol]) return;
     const uint32_t o = d.lo + ol;
+    if ((mode == 0 && tgt[ol] < 0) || (mode == 1 && !failed[ol])) {
+        // (not a sender of this phase: the phase's receive waves read sS[o] to learn whether their own row is pending)
+        if (sS && lane_id() == 0) sS[o] = SRC_NONE;
+        return;
+    }
     // (the row's other reads go with the issue's own first loads: nothing below waits for a round trip of its own)
     const uint32_t dirty = d.dirty[ol], cpslot = d.cpslot[ol], cs = d.cs[ol], selfw = d.mw[(size_t)ol * d.NP + o];
+    const uint32_t clen = d.clen[ol];
+    const int32_t clast = d.clast[ol];
     MsgDesc md;
     wave_issue(d, ol, md);
     uint32_t slot = SRC_NONE;
-    if (sS && dirty) {
+    if (sS && dirty && !d.ulog) {                                   // (no undo log: the row is copied)
         MsgDesc sn;
         if (wave_snapshot(d, ol, o, sn)) slot = sn.off_lo;
+        if (lane_id() == 0) ctr_add(d, C_X_ISSUE_SNAPS, 1ull);
+    } else if (sS && dirty) {
+        // pending, live: no copy. The row's issue-time content is rebuilt from the live row and the phase's undo log
+        // if a decision ever needs it (wave_rebuild_issue_row); what a snapshot's hash needs beside the words is kept
+        slot = SRC_PEND;
+        if (lane_id() == 0) { d.ilen[ol] = clen; d.ilast[ol] = clast; }
     } else if (sS) {
         slot = cpslot;                                           // clean, checksum still on the side stream
     }
@@ -1362,7 +1452,8 @@ struct RecvArgs {
     int phase;                                      // 0: direct ping (phase D), 1: ping-req (Q2)
     const MsgDesc *sdesc;                           // sender snapshots (by global sender id)
     const uint32_t *sI, *sC;
-    const uint32_t *sS;                             // lazy sender checksum: dense slot of the sender's row, or none
+    uint32_t *sS;                                   // lazy sender checksum: dense slot of the sender's row, SRC_PEND
+                                                    // (pending, live: published here if a receive wave rebuilds it), or none
     MsgDesc *rdesc;                                 // responses (by sender id / sender id * K + slot)
     uint4 *defer;                                   // {resp index | rdirty<<31, receiver slot, sender checksum or
                                                     //  slot, pair index | spending<<31}
@@ -1398,7 +1489,7 @@ __global__ void k_pair_info(const DS d, const uint32_t *vals, uint32_t n, int ph
 // heal rounds did, sharded): a dense message, or a bound above 4,096 records or a sixteenth of a sub-pool, allocates
 // the exact count after the merge (at most 4,096 spare records per receiver).
 __device__ __forceinline__ void recv_one_pre(const DS &d, const RecvArgs &a, uint32_t j, const uint4 pi0, const uint4 pi1,
-                                             uint32_t pair, uint32_t nslots, RowPre &p) {
+                                             uint32_t pair, uint32_t nslots, RowPre &p, LazyCtx &lz) {
     const uint32_t ol = j - d.lo;
     const uint32_t v = pi1.w, sender = a.phase == 0 ? v : v / d.K, resp_idx = v;
     MsgDesc md;
@@ -1407,7 +1498,7 @@ __device__ __forceinline__ void recv_one_pre(const DS &d, const RecvArgs &a, uin
     const bool early = md.kind == 0 && bound > 0 && bound <= min(4096ull, d.pool_cap / POOL_SHARDS / 16);
     unsigned long long roff = 0;
     if (early && lane_id() == 0) roff = pool_alloc_lane0(d, (uint32_t)bound);   // (read after the merge)
-    wave_merge_msg_pre(d, ol, j, md, a.r, a.r, 0, p, -1, nullptr, true);
+    wave_merge_msg_pre(d, ol, j, md, a.r, a.r, 0, p, -1, nullptr, true, &lz);
     MsgDesc resp;
     resp.kind = 0; resp.len = 0; resp.off_lo = resp.off_hi = 0;
     uint32_t kept = 0;
@@ -1480,9 +1571,12 @@ __global__ void __launch_bounds__(256, RECV_MIN_WAVES) k_recv(DS d, RecvArgs a) 
     const uint32_t n = a.counts[u], off = a.offs[u];
     RowPre p = row_pre(d, key - d.lo);
     const uint32_t nslots = d.hidx ? d.hot_cnt[0] : 0u;
+    LazyCtx lz;
+    lz.sS = a.sS; lz.sI = a.sI;
+    lz.pend = a.sS && d.ulog && uni(a.sS[key]) == SRC_PEND;        // this row is a pending-live sender of the phase
     for (uint32_t w = 0; w < n; w++) {
         const uint32_t pair = off + w;
-        recv_one_pre(d, a, key, a.pinfo[2 * (size_t)pair], a.pinfo[2 * (size_t)pair + 1], pair, nslots, p);
+        recv_one_pre(d, a, key, a.pinfo[2 * (size_t)pair], a.pinfo[2 * (size_t)pair + 1], pair, nslots, p, lz);
     }
     if (d.ulog_cnt && lane_id() == 0) d.ulog_cnt[key - d.lo] = min(p.ulog, d.ulog_cap + 1u);
 }
@@ -1611,31 +1705,35 @@ __device__ bool wave_rows_differ(const DS &d, const uint32_t *a, const uint32_t 
 }
 
 // one wave: does snapshot a differ from live row b as it was before its logged merges (the first logged old word of each
-// member restored; nlog <= d.ulog_cap <= 64 entries of log, one per lane, members inside the divergent columns: every
-// row-word write marks its column)? Only over the divergent columns; false when they are more than N/4 (the caller
-// hashes instead)
+// member restored; nlog <= d.ulog_cap entries of log, walked in chunks of 64, one entry per lane, members inside the
+// divergent columns: every row-word write marks its column)? Over the divergent columns while they are at most N/4.
+// With more, full = false declines (done = false: the caller hashes instead) and full = true compares every member.
 __device__ bool wave_rows_differ_undo(const DS &d, const uint32_t *a, const uint32_t *b, const uint2 *log, uint32_t nlog,
-                                      bool &done) {
+                                      bool &done, bool full = false) {
     const uint32_t lane = lane_id();
-    const uint32_t nu = d.ucnt[0];
-    done = nu <= d.N / 4;
+    const bool bycol = d.ucnt[0] <= d.N / 4;
+    const uint32_t nu = bycol ? d.ucnt[0] : d.N;
+    done = bycol || full;
     if (!done) return true;
-    const uint2 L = lane < nlog ? log[lane] : make_uint2(0xFFFFFFFFu, 0u);
     bool diff = false;
     for (uint32_t c0 = 0; c0 < nu && !__any(diff); c0 += 64 * MB) {
         uint32_t m[MB], x[MB], y[MB];
 #pragma unroll
         for (int u = 0; u < MB; u++) {
             const uint32_t c = c0 + u * 64 + lane;
-            m[u] = c < nu ? d.ucl[c] : 0xFFFFFFFEu;
+            m[u] = c >= nu ? 0xFFFFFFFEu : bycol ? d.ucl[c] : c;
             x[u] = c < nu ? a[m[u]] : 0u;
             y[u] = c < nu ? b[m[u]] : 0u;
         }
-        for (int k = (int)nlog - 1; k >= 0; k--) {               // (descending: the first logged word of a member wins)
-            const uint32_t lm = (uint32_t)__builtin_amdgcn_readlane((int)L.x, k);
-            const uint32_t lw = (uint32_t)__builtin_amdgcn_readlane((int)L.y, k);
+        // (descending, chunk by chunk and entry by entry: the first logged word of a member wins)
+        for (int k0 = nlog ? (int)((nlog - 1u) & ~63u) : -1; k0 >= 0; k0 -= 64) {
+            const uint2 L = (uint32_t)k0 + lane < nlog ? log[(uint32_t)k0 + lane] : make_uint2(0xFFFFFFFFu, 0u);
+            for (int k = (int)min(64u, nlog - (uint32_t)k0) - 1; k >= 0; k--) {
+                const uint32_t lm = (uint32_t)__builtin_amdgcn_readlane((int)L.x, k);
+                const uint32_t lw = (uint32_t)__builtin_amdgcn_readlane((int)L.y, k);
 #pragma unroll
-            for (int u = 0; u < MB; u++) y[u] = m[u] == lm ? lw : y[u];
+                for (int u = 0; u < MB; u++) y[u] = m[u] == lm ? lw : y[u];
+            }
         }
 #pragma unroll
         for (int u = 0; u < MB; u++) diff |= x[u] != y[u];
@@ -1647,8 +1745,9 @@ __device__ bool wave_rows_differ_undo(const DS &d, const uint32_t *a, const uint
 // the job is queued at once; heal runs in phase E, before any phase-D job of the round)
 // Equal rows have equal checksums: a deferred decision whose receiver snapshot equals the sender's
 // issue-time row (word for word) is "no full sync" without hashing either side. The sender's
-// issue-time row is its issue snapshot (pending C_o, local or side slot) or, for a sender that was
-// clean at issue and is still clean, its current row. Remote senders and heal pings are not checked.
+// issue-time row is its snapshot (a side slot, or a pending-live sender's rebuilt row), a pending-live
+// sender's live row with the phase's undo log applied backwards or, for a sender that was clean at
+// issue and is still clean, its current row. Remote senders and heal pings are not checked.
 // Checksum representatives (round 6). A sender that was clean at issue gave its checksum C_o, but its row may have
 // changed since (it received pings of its own in phase D): then no issue-time row was left to compare with, and the
 // decision hashed the receiver's snapshot (a one-row chain, 3.3 ms, on the round's critical path in the cascade's
@@ -1677,18 +1776,28 @@ __device__ __forceinline__ uint32_t rep_find(const DS &d, const unsigned long lo
     return r < d.NL && !d.dirty[r] && d.cpslot[r] == SRC_NONE && d.cs[r] == cs ? r : SRC_NONE;
 }
 
+// the lazy slot of a deferred decision's local pending sender as it is now (z: the pair's copy of sS[sender], taken
+// before the receive waves ran; sS: the phase's array, null in the heal ping's resolution)
+__device__ __forceinline__ uint32_t lazy_slot(uint32_t z, const uint32_t *sS, uint32_t sender) {
+    return z == SRC_PEND && sS ? sS[sender] : z;
+}
+
 __global__ void k_defer_eq(DS d, const uint4 *defer, const uint32_t *defer_cnt, int phase, uint8_t *eq,
-                           const unsigned long long *tab, uint32_t mask, uint32_t gen) {
+                           const unsigned long long *tab, uint32_t mask, uint32_t gen, const uint32_t *sS) {
     const uint32_t i = wave_gid();
     if (i >= *defer_cnt) return;
     const uint4 e = defer[i];
     const uint32_t ri = e.x & 0x7FFFFFFFu, sender = phase == 1 ? ri / d.K : ri;
     const uint32_t *srow = nullptr;
-    bool viarep = false;
+    bool viarep = false, pendlive = false;
     const uint32_t dt = d.defer_test;                              // (tests: bits 1, 2, 4 skip a way each)
     if (phase != 2) {
         if (e.w & 0x80000000u) {
-            if (!(e.z & 0x80000000u)) srow = d.dense + (size_t)e.z * d.NP;
+            // a pending sender's state is read now: its receive wave may have rebuilt and published its issue-time row
+            // after the pair's snapshot (e.z) was taken
+            const uint32_t z = lazy_slot(e.z, sS, sender);
+            if (z == SRC_PEND) pendlive = true;
+            else if (!(z & 0x80000000u) && z != SRC_CLAIM) srow = d.dense + (size_t)z * d.NP;
         } else if (!(dt & 1u) && sender >= d.lo && sender < d.lo + d.NL && !d.dirty[sender - d.lo]) {
             srow = d.mw + (size_t)(sender - d.lo) * d.NP;
         } else if (tab && !(dt & 2u)) {                            // C_o = e.z known: a representative of it
@@ -1702,6 +1811,15 @@ __global__ void k_defer_eq(DS d, const uint4 *defer, const uint32_t *defer_cnt, 
     bool same = false, viaundo = false, over = false;
     if (srow) {
         same = !wave_rows_differ(d, d.dense + (size_t)e.y * d.NP, srow, nullptr, nullptr);
+    } else if (pendlive) {
+        // pending, live: the sender's row has changed since issue only by this phase's logged merges (a log that would
+        // have overflowed, or a dense merge, rebuilt the row first), so the live row with the log undone is its
+        // issue-time row, whatever the number of divergent columns. No test bit switches this off: it stands for
+        // the comparison with the issue snapshot, and counts as that one (defer_eq).
+        const uint32_t sl = sender - d.lo;
+        bool done = false;
+        same = !wave_rows_differ_undo(d, d.dense + (size_t)e.y * d.NP, d.mw + (size_t)sl * d.NP,
+                                      d.ulog + (size_t)sl * d.ulog_stride, min(d.ulog_cnt[sl], d.ulog_cap), done, true);
     } else if (phase != 2 && !(e.w & 0x80000000u) && d.ulog && !(dt & 4u) && sender >= d.lo && sender < d.lo + d.NL) {
         // the sender was clean at issue (C_o = e.z) and has changed since only by this phase's merges: its issue-time
         // row is its row with the logged words restored (a sender that received nothing this phase has an empty log:
@@ -1711,7 +1829,7 @@ __global__ void k_defer_eq(DS d, const uint4 *defer, const uint32_t *defer_cnt, 
         if (!over) {
             bool done = false;
             const bool differ = wave_rows_differ_undo(d, d.dense + (size_t)e.y * d.NP, d.mw + (size_t)sl * d.NP,
-                                                      d.ulog + (size_t)sl * ULOG_CAP, nlog, done);
+                                                      d.ulog + (size_t)sl * d.ulog_stride, nlog, done);
             viaundo = done;
             same = done && !differ;
         }
@@ -1721,14 +1839,44 @@ __global__ void k_defer_eq(DS d, const uint4 *defer, const uint32_t *defer_cnt, 
         ctr_add(d, C_X_DEFER, 1ull);
         if (same) ctr_add(d, viarep ? C_X_DEFER_REP : viaundo ? C_X_DEFER_UNDO : C_X_DEFER_EQ, 1ull);
         else if (viarep || viaundo) ctr_add(d, viarep ? C_X_DEFER_REP_DIFF : C_X_DEFER_UNDO_DIFF, 1ull);
-        if (!srow && !viaundo) ctr_add(d, C_X_DEFER_NOROW, 1ull);
+        if (!srow && !viaundo && !pendlive) ctr_add(d, C_X_DEFER_NOROW, 1ull);
         if (over) ctr_add(d, C_X_DEFER_UNDO_OVER, 1ull);
         if (!(e.w & 0x80000000u)) ctr_add(d, C_X_DEFER_CLEAN, 1ull);
     }
 }
 
+// Pending-live senders whose checksum is needed after all: the deferred decisions that row equality did not settle
+// (eq[i] = 0; req = null) or the senders other shards ask about (req = the imported P_CSREQ, defer = eq = null). One wave
+// per entry rebuilds the sender's issue-time row and publishes it in sS[sender]; the exchange on sS makes it once per
+// sender, however many helpers deferred on it. Runs before the lists of rows to hash are made.
+__global__ void k_lazy_mat(DS d, const uint4 *defer, const uint8_t *eq, const uint4 *req, const uint32_t *cnt, uint32_t cap,
+                           int phase, uint32_t *sS, const uint32_t *sI) {
+    const uint32_t i = wave_gid();
+    if (i >= *cnt || i >= cap) return;
+    uint32_t sender;
+    if (req) {
+        if (req[i].y != SRC_PEND) return;
+        sender = req[i].x;
+    } else {
+        const uint4 e = defer[i];
+        if (eq[i] || !(e.w & 0x80000000u) || e.z != SRC_PEND) return;
+        const uint32_t ri = e.x & 0x7FFFFFFFu;
+        sender = phase == 1 ? ri / d.K : ri;
+    }
+    if (sender < d.lo || sender >= d.lo + d.NL) return;
+    uint32_t won = 0;
+    if (lane_id() == 0) won = atomicCAS(&sS[sender], SRC_PEND, SRC_CLAIM) == SRC_PEND;
+    if (!__builtin_amdgcn_readlane((int)won, 0)) return;
+    const uint32_t sl = sender - d.lo;
+    const uint32_t slot = wave_rebuild_issue_row(d, sl, sender, sI[sender], min(d.ulog_cnt[sl], d.ulog_cap));
+    if (lane_id() == 0) {
+        if (slot != SRC_NONE) sS[sender] = slot;
+        ctr_add(d, C_X_LAZY_MAT, 1ull);
+    }
+}
+
 __global__ void k_recv_finish(DS d, const uint4 *defer, const uint32_t *defer_cnt, MsgDesc *rdesc, int phase,
-                              uint8_t *fsflag, const uint32_t *rcs, const uint8_t *eq) {
+                              uint8_t *fsflag, const uint32_t *rcs, const uint8_t *eq, const uint32_t *sS) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= *defer_cnt) return;
     const uint4 e = defer[i];
@@ -1739,7 +1887,9 @@ __global__ void k_recv_finish(DS d, const uint4 *defer, const uint32_t *defer_cn
     resp.kind = 0; resp.len = 0; resp.off_lo = resp.off_hi = 0;
     bool differ = false;
     if (!eq[i]) {
-        const uint32_t scs = !(e.w & 0x80000000u) ? e.z : (e.z & 0x80000000u) ? rcs[sender] : d.dense_cs[e.z];
+        const uint32_t z = (e.w & 0x80000000u) ? lazy_slot(e.z, sS, sender) : 0u;   // (rebuilt by k_lazy_mat at the latest)
+        const uint32_t scs = !(e.w & 0x80000000u) ? e.z : (z & 0x80000000u) ? rcs[sender] :
+                             z < SRC_CLAIM ? d.dense_cs[z] : 0u;   // (not rebuilt: the pool was full, E_DENSE is set)
         const uint32_t alias = d.dense_meta[slot].w;               // receiver clean, hashed on the side stream
         if (alias) d.dense_cs[slot] = d.dense_cs[alias - 1u];
         differ = d.dense_cs[slot] != scs;
@@ -1763,14 +1913,16 @@ __global__ void k_recv_finish(DS d, const uint4 *defer, const uint32_t *defer_cn
 // defer list → checksum list of the dense snapshots that need a hash (NL + slot): dirty receivers and
 // pending senders (a sender referenced by several deferred decisions is hashed once per reference)
 __global__ void k_defer_ids(DS d, const uint4 *defer, const uint32_t *defer_cnt, const uint8_t *eq, uint32_t *list,
-                            uint32_t *cnt) {
+                            uint32_t *cnt, int phase, const uint32_t *sS) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= *defer_cnt || eq[i]) return;
     atomicAdd(cnt + 1, 1u);                                        // decisions left to the checksums
     const uint4 e = defer[i];
     if (e.x & 0x80000000u) list[atomicAdd(cnt, 1u)] = d.NL + e.y;
-    if ((e.w & 0x80000000u) && !(e.z & 0x80000000u) && e.z < d.dense_cap)                  // local pending
-        list[atomicAdd(cnt, 1u)] = d.NL + e.z;                     // (slots >= dense_cap: side stream)
+    const uint32_t ri = e.x & 0x7FFFFFFFu, sender = phase == 1 ? ri / d.K : ri;
+    const uint32_t z = lazy_slot(e.z, sS, sender);
+    if ((e.w & 0x80000000u) && !(z & 0x80000000u) && z < d.dense_cap)                      // local pending
+        list[atomicAdd(cnt, 1u)] = d.NL + z;                       // (slots >= dense_cap: side stream)
 }
 
 // tryStartReverseFullSync (disseminator.go:257-278) in inbox order: at most maxjobs per receiver

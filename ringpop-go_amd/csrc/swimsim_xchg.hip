@@ -244,19 +244,23 @@ __global__ void k_x_csreq(DS d, const uint4 *defer, const uint32_t *defer_cnt, i
 }
 
 // requested snapshots → checksum list (after the local deferred ids)
-__global__ void k_csreq_ids(DS d, const uint4 *csreq, const uint32_t *csreqcnt, uint32_t *list, uint32_t *cnt) {
+// (a pending-live sender's slot is read from sS now: k_lazy_mat has just rebuilt its issue-time row)
+__global__ void k_csreq_ids(DS d, const uint4 *csreq, const uint32_t *csreqcnt, uint32_t *list, uint32_t *cnt,
+                            const uint32_t *sS) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= *csreqcnt) return;
-    if (csreq[i].y < d.dense_cap) list[atomicAdd(cnt, 1u)] = d.NL + csreq[i].y;   // else hashed on the side stream
+    const uint32_t z = lazy_slot(csreq[i].y, sS, csreq[i].x);
+    if (z < d.dense_cap) list[atomicAdd(cnt, 1u)] = d.NL + z;   // else hashed on the side stream
 }
 
 // answers to the requesting shards
 __global__ void k_x_csresp(DS d, const uint4 *csreq, const uint32_t *csreqcnt, uint4 *items, uint32_t *cnt,
-                           uint32_t cap) {
+                           uint32_t cap, const uint32_t *sS) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= *csreqcnt) return;
     const uint4 r = csreq[i];
-    x_push(items, cnt, cap, d.err, make_uint4(r.z, P_CSRESP, r.x, d.dense_cs[r.y]));
+    const uint32_t z = lazy_slot(r.y, sS, r.x);
+    x_push(items, cnt, cap, d.err, make_uint4(r.z, P_CSRESP, r.x, z < SRC_CLAIM ? d.dense_cs[z] : 0u));
 }
 
 // responses of local receivers to remote senders (after the receive waves resolved them)
