@@ -50,6 +50,33 @@ int swimring_lookup_batch(swimring_t *r, const uint8_t *keys, const uint64_t *of
  * reference returns them from a map) */
 int swimring_lookup_n(swimring_t *r, const uint8_t *key, size_t len, uint32_t n, int32_t *out, size_t *nout);
 
+/* LookupN for a batch of keys in one launch (one wave per key; keys packed as for swimring_lookup_batch):
+ * out[k*n + j], j < cnt[k], are key k's owners, the rest of the row is -1. cnt[k] <= min(n, server count).
+ * The owners of one key come in ring-walk order: from the first point >= Fingerprint32(key), wrapping once,
+ * each distinct owner at its first occurrence. That is stronger than the reference, which returns them from
+ * a Go map in no order (hashring.go:279-301), and makes the single-key preference list (replicator.go:211-213)
+ * deterministic. n >= server count gives every server in ascending id, as in swimring_lookup_n; n == 0 or an
+ * empty ring gives cnt[k] = 0. nkeys == 0 is accepted and touches nothing. SWIMSIM_EINVAL: a NULL argument, or
+ * nkeys * n above 2^31 - 1 (checked before anything is allocated). SWIMSIM_ENOMEM: a device buffer could not
+ * grow; the handle stays usable. */
+int swimring_lookup_n_batch(swimring_t *r, const uint8_t *keys, const uint64_t *off, size_t nkeys, uint32_t n,
+                            int32_t *out, uint32_t *cnt);
+
+/* groupReplicas (replica/replicator.go:170-191): the same matrix (out and cnt may be NULL) and its inverse,
+ * keysByDest, as CSR. dest[d], d < *ndest, are the server ids that own at least one key, ascending; the indices
+ * of the keys dest[d] owns are key_idx[dest_off[d] .. dest_off[d+1]), ascending (the reference appends in key
+ * order); a key given twice is two indices. The matrix stays on the device between the lookup and the inversion
+ * (a radix sort of owner << 32 | key index and a boundary pass). Caller sizes: dest holds server count entries,
+ * dest_off server count + 1, key_idx nkeys * min(n, server count). nkeys == 0, n == 0 or an empty ring give
+ * *ndest = 0 and dest_off[0] = 0. Errors as swimring_lookup_n_batch. */
+int swimring_group_replicas(swimring_t *r, const uint8_t *keys, const uint64_t *off, size_t nkeys, uint32_t n,
+                            int32_t *out, uint32_t *cnt, int32_t *dest, uint64_t *dest_off, uint32_t *key_idx,
+                            size_t *ndest);
+
+/* measurement: HIP-event ms of the last batched LookupN kernel (by either call above) and of the last grouping
+ * (sort + boundaries). swimring_last_times is not affected by these calls. */
+int swimring_last_replica_times(swimring_t *r, double *lookup_n_ms, double *group_ms);
+
 /* server id -> name (ids are stable for the handle's lifetime) */
 const char *swimring_server_name(swimring_t *r, int32_t id);
 

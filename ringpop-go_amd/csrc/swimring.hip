@@ -12,6 +12,8 @@
 //   k_ring_points   replica hashes of the removed servers (hash only), radix sort
 //   k_ring_drop     drop every ring point whose hash is one of them (rbtree Delete by value)
 // Lookups: one lane per key hashes it and binary-searches the ring (lower bound, wrap to 0).
+// LookupN for a batch: one wave per key walks the ring 64 points per step (k_ring_lookup_n_batch); groupReplicas
+// inverts the owner matrix with a radix sort of (owner << 32 | key index) and a boundary pass.
 #include "../../include/swimring.h"
 #include "../../include/swimsim.h"
 #include "swimsim_device.h"
@@ -182,6 +184,138 @@ __global__ void k_ring_lookup_n(const uint8_t *key, uint32_t len, const unsigned
     *nout = got;
 }
 
+// ---------------------------------------------------------------------------------------------
+// LookupN for a batch of keys: one wave per key, LN_WAVES keys in flight per workgroup. Every lane hashes the
+// key (wave-uniform addresses, so the hash is scalar) and the wave finds the lower bound together
+// (wave_lower_bound_u64); then it loads 64 consecutive points per step (index modulo P, at most P points in
+// all). A lane's owner is a candidate if it is not among the owners taken so far:
+//   n <= LN_LIST_MAX  the taken owners are a list in LDS (at most n - 1 broadcast reads per step);
+//   n >  LN_LIST_MAX  they are a bitmap over server ids, one slice per wave of the grid in device scratch,
+//                     zero at entry and cleared again bit by bit when the key is done (BITMAP).
+// Candidates that repeat a lower lane's owner are dropped without touching memory: the lowest candidate's owner
+// is read with readlane, one ballot finds every lane holding it, and the loop ends once n - got distinct
+// owners are found. The popcount of the new lanes below a lane is its output slot.
+// The wave's lanes read what other lanes of the same wave wrote one step earlier (list, bitmap, output row):
+// those accesses are atomic loads / stores with a wavefront-scope fence between the steps.
+// ---------------------------------------------------------------------------------------------
+constexpr uint32_t LN_WAVES = 4;
+constexpr uint32_t LN_LIST_MAX = 16;
+constexpr uint32_t LN_MAX_WAVES = 8192;                           // bitmap mode: 256 CUs x 32 waves
+constexpr size_t LN_SEEN_BYTES = (size_t)64 << 20;                // bitmap mode: scratch budget for the slices
+
+__device__ __forceinline__ uint32_t ld_lanes(const uint32_t *p) {
+    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ void st_lanes(uint32_t *p, uint32_t v) {
+    __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ void fence_lanes() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// lower_bound_u64 by a whole wave: each step the lanes probe up to 64 evenly spaced points of the remaining range
+// and one ballot keeps the gap the bound lies in, so a ring of P points takes log65 P dependent loads, not log2 P
+__device__ __forceinline__ uint32_t wave_lower_bound_u64(const unsigned long long *a, uint32_t n, unsigned long long x,
+                                                         uint32_t lane) {
+    uint64_t lo = 0, hi = n;                                      // a[i] < x below lo, a[i] >= x from hi on
+    while (lo < hi) {
+        const uint64_t step = (hi - lo + 63) / 64;
+        const uint64_t i = lo + lane * step;
+        const uint32_t c = (uint32_t)__popcll(__ballot(i < hi && a[i] < x));   // sorted: a prefix of the probes
+        if (c == 0) break;                                        // a[lo] >= x
+        if (lo + c * step < hi) hi = lo + c * step;               // probe c, if there is one, is >= x
+        lo += (c - 1) * step + 1;                                 // probe c - 1 is < x
+    }
+    return (uint32_t)lo;
+}
+
+template <bool BITMAP>
+__global__ __launch_bounds__(LN_WAVES * 64) void k_ring_lookup_n_batch(
+    const uint8_t *bytes, const uint64_t *off, uint32_t nkeys, const unsigned long long *ring, uint32_t P, uint32_t n,
+    int32_t *out, uint32_t *cnt, uint32_t *seen, uint32_t seen_words) {
+    __shared__ uint32_t taken[LN_WAVES][LN_LIST_MAX];
+    const uint32_t lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const uint32_t wave = blockIdx.x * LN_WAVES + w, nwaves = gridDim.x * LN_WAVES;
+    uint32_t *bits = BITMAP ? seen + (size_t)wave * seen_words : nullptr;
+    const unsigned long long below = (1ull << lane) - 1;
+    for (uint64_t k = wave; k < nkeys; k += nwaves) {
+        const uint64_t a = off[k];
+        const uint32_t h = __builtin_amdgcn_readfirstlane(fp32_dev(bytes + a, (uint32_t)(off[k + 1] - a)));
+        uint32_t start = __builtin_amdgcn_readfirstlane(wave_lower_bound_u64(ring, P, (unsigned long long)h << 32, lane));
+        if (start == P) start = 0;
+        uint32_t *row = (uint32_t *)out + k * n;
+        uint32_t got = 0;
+        for (uint64_t base = 0; base < P && got < n; base += 64) {
+            const uint64_t idx = base + lane;
+            const bool valid = idx < P;
+            uint64_t p = start + idx;
+            if (p >= P) p -= P;
+            const uint32_t o = valid ? (uint32_t)ring[p] : 0;
+            bool cand = valid;
+            if (BITMAP) {
+                if (valid) cand = !((ld_lanes(bits + (o >> 5)) >> (o & 31)) & 1);
+            } else {
+                for (uint32_t q = 0; q < got; q++) cand = cand && ld_lanes(&taken[w][q]) != o;
+            }
+            unsigned long long m = __ballot(cand), fresh = 0;
+            const uint32_t need = n - got;
+            uint32_t nf = 0;
+            while (m && nf < need) {
+                const uint32_t j = (uint32_t)__builtin_ctzll(m);
+                const uint32_t oj = (uint32_t)__builtin_amdgcn_readlane((int)o, (int)j);
+                fresh |= 1ull << j;
+                nf++;
+                m &= ~__ballot(cand && o == oj);                  // lane j and every repeat of its owner
+            }
+            if ((fresh >> lane) & 1) {
+                const uint32_t slot = got + (uint32_t)__popcll(fresh & below);
+                st_lanes(row + slot, o);
+                if (BITMAP) atomicOr(bits + (o >> 5), 1u << (o & 31));
+                else st_lanes(&taken[w][slot], o);                // slot < n <= LN_LIST_MAX
+            }
+            got += nf;
+            fence_lanes();
+        }
+        if (BITMAP)                                               // leave the slice zero for the wave's next key
+            for (uint32_t j = lane; j < got; j += 64) st_lanes(bits + (ld_lanes(row + j) >> 5), 0);
+        for (uint32_t j = got + lane; j < n; j += 64) row[j] = 0xffffffffu;
+        if (lane == 0) cnt[k] = got;
+        fence_lanes();
+    }
+}
+
+// n >= server count: every key's owners are every server, ascending id (lookupNNoLock's shortcut)
+__global__ void k_ring_fill_all(const int32_t *all, uint32_t nall, uint32_t n, uint64_t total, int32_t *out,
+                                uint32_t *cnt) {
+    const uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= total) return;
+    const uint32_t j = (uint32_t)(e % n);
+    out[e] = j < nall ? all[j] : -1;
+    if (j == 0) cnt[e / n] = nall;
+}
+
+// groupReplicas: entry e = (key k, column j) of the owner matrix becomes the sort key owner << 32 | k; the -1
+// padding sorts behind every server
+__global__ void k_group_keys(const int32_t *mat, uint32_t n, uint64_t total, unsigned long long *keys) {
+    const uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= total) return;
+    keys[e] = ((unsigned long long)(uint32_t)mat[e] << 32) | (uint32_t)(e / n);
+}
+
+// sorted keys: key_idx[e] = the key index; the first entry of each destination (and of the padding) is
+// flagged and carries destination << 32 | e
+__global__ void k_group_bounds(const unsigned long long *skeys, uint64_t total, uint32_t *key_idx, uint8_t *flag,
+                               unsigned long long *bound) {
+    const uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= total) return;
+    const uint32_t d = (uint32_t)(skeys[e] >> 32);
+    key_idx[e] = (uint32_t)skeys[e];
+    flag[e] = e == 0 || (uint32_t)(skeys[e - 1] >> 32) != d ? 1 : 0;
+    bound[e] = ((unsigned long long)d << 32) | e;
+}
+
 uint32_t grid_for(uint64_t n) { return (uint32_t)std::max<uint64_t>(1, (n + 255) / 256); }
 
 }  // namespace
@@ -225,6 +359,11 @@ struct swimring {
     size_t out_cap = 0;
     hipEvent_t e0 = nullptr, e1 = nullptr;
     double t_add = 0, t_look = 0;
+    // LookupN batch / groupReplicas: owner matrix [nkeys x n] (its counts are uout), the waves' seen-bitmap slices
+    int32_t *mat = nullptr;
+    uint32_t *wseen = nullptr;
+    size_t mat_cap = 0, wseen_cap = 0;
+    double t_lookn = 0, t_group = 0;
 
     int fail(int code, const char *fmt, ...) {
         char buf[512];
@@ -375,6 +514,55 @@ int compute_checksum(swimring *r) {
     return 0;
 }
 
+// nkeys * n matrix entries are sort items (int) and CSR positions (u32)
+bool replica_dims_ok(size_t nkeys, uint32_t n) {
+    return nkeys <= 0x7fffffffu && (n == 0 || nkeys <= (size_t)0x7fffffffu / n);
+}
+
+// LookupN of nkeys keys (nkeys, n > 0) into r->mat [nkeys x n] and r->uout [nkeys]; both stay on the device
+int lookup_n_device(swimring *r, const uint8_t *keys, const uint64_t *off, size_t nkeys, uint32_t n) {
+    const size_t total = nkeys * n;
+    size_t c = r->mat_cap;
+    if (int rc = grow(r, &r->mat, &c, total)) return rc;
+    r->mat_cap = c;
+    if (int rc = upload_keys(r, keys, off, nkeys)) return rc;
+    std::vector<int32_t> all;
+    if (n >= r->nset) {                                           // lookupNNoLock: every server
+        for (size_t i = 0; i < r->names.size(); i++)
+            if (r->in_set[i]) all.push_back((int32_t)i);
+        c = r->bid_cap;
+        if (int rc = grow(r, &r->bid, &c, std::max<size_t>(all.size(), 1))) return rc;
+        r->bid_cap = c;
+        if (!all.empty()) RCHK(r, hipMemcpyAsync(r->bid, all.data(), all.size() * 4, hipMemcpyHostToDevice, r->s));
+        RCHK(r, hipEventRecord(r->e0, r->s));
+        hipLaunchKernelGGL(k_ring_fill_all, dim3(grid_for(total)), dim3(256), 0, r->s, r->bid, (uint32_t)all.size(), n,
+                           (uint64_t)total, r->mat, r->uout);
+    } else if (n <= LN_LIST_MAX) {
+        RCHK(r, hipEventRecord(r->e0, r->s));
+        hipLaunchKernelGGL(k_ring_lookup_n_batch<false>, dim3((uint32_t)((nkeys + LN_WAVES - 1) / LN_WAVES)),
+                           dim3(LN_WAVES * 64), 0, r->s, r->bytes, r->boff, (uint32_t)nkeys, r->ring, r->P, n, r->mat,
+                           r->uout, (uint32_t *)nullptr, 0u);
+    } else {
+        const size_t words = (r->names.size() + 31) / 32;
+        const size_t waves = std::min<size_t>(std::max<size_t>(LN_SEEN_BYTES / (words * 4), LN_WAVES), LN_MAX_WAVES);
+        const size_t blocks = std::min((nkeys + LN_WAVES - 1) / LN_WAVES, waves / LN_WAVES);
+        c = r->wseen_cap;
+        if (int rc = grow(r, &r->wseen, &c, blocks * LN_WAVES * words)) return rc;
+        r->wseen_cap = c;
+        RCHK(r, hipMemsetAsync(r->wseen, 0, blocks * LN_WAVES * words * 4, r->s));
+        RCHK(r, hipEventRecord(r->e0, r->s));
+        hipLaunchKernelGGL(k_ring_lookup_n_batch<true>, dim3((uint32_t)blocks), dim3(LN_WAVES * 64), 0, r->s, r->bytes,
+                           r->boff, (uint32_t)nkeys, r->ring, r->P, n, r->mat, r->uout, r->wseen, (uint32_t)words);
+    }
+    RCHK(r, hipGetLastError());
+    RCHK(r, hipEventRecord(r->e1, r->s));
+    RCHK(r, hipStreamSynchronize(r->s));                         // all is a host temporary
+    float ms = 0;
+    hipEventElapsedTime(&ms, r->e0, r->e1);
+    r->t_lookn = ms;
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -398,7 +586,7 @@ int swimring_destroy(swimring_t *r) {
     if (!r) return SWIMSIM_OK;
     if (r->s) hipStreamSynchronize(r->s);
     void *bufs[] = {r->dnames, r->dnoff, r->dnlen, r->ring, r->ring2, r->k0, r->k1, r->kept, r->v0, r->v1, r->nsel,
-                    r->flag, r->bid, r->cub, r->bytes, r->boff, r->iout, r->uout, r->seen};
+                    r->flag, r->bid, r->cub, r->bytes, r->boff, r->iout, r->uout, r->seen, r->mat, r->wseen};
     for (void *p : bufs)
         if (p) hipFree(p);
     if (r->e0) hipEventDestroy(r->e0);
@@ -576,6 +764,91 @@ int swimring_lookup_n(swimring_t *r, const uint8_t *key, size_t len, uint32_t n,
     RCHK(r, hipMemcpyAsync(out, r->iout, (size_t)got * 4, hipMemcpyDeviceToHost, r->s));
     RCHK(r, hipStreamSynchronize(r->s));
     *nout = got;
+    return SWIMSIM_OK;
+}
+
+int swimring_lookup_n_batch(swimring_t *r, const uint8_t *keys, const uint64_t *off, size_t nkeys, uint32_t n,
+                            int32_t *out, uint32_t *cnt) {
+    if (!r || !off || !cnt) return SWIMSIM_EINVAL;
+    if (nkeys == 0) return SWIMSIM_OK;
+    if (!keys && off[nkeys]) return SWIMSIM_EINVAL;
+    if (!replica_dims_ok(nkeys, n)) return r->fail(SWIMSIM_EINVAL, "nkeys * n exceeds 2^31 - 1 entries");
+    if (n == 0) {
+        memset(cnt, 0, nkeys * sizeof *cnt);
+        return SWIMSIM_OK;
+    }
+    if (!out) return SWIMSIM_EINVAL;
+    if (int rc = lookup_n_device(r, keys, off, nkeys, n)) return rc;
+    RCHK(r, hipMemcpyAsync(out, r->mat, nkeys * n * 4, hipMemcpyDeviceToHost, r->s));
+    RCHK(r, hipMemcpyAsync(cnt, r->uout, nkeys * 4, hipMemcpyDeviceToHost, r->s));
+    RCHK(r, hipStreamSynchronize(r->s));
+    return SWIMSIM_OK;
+}
+
+int swimring_group_replicas(swimring_t *r, const uint8_t *keys, const uint64_t *off, size_t nkeys, uint32_t n,
+                            int32_t *out, uint32_t *cnt, int32_t *dest, uint64_t *dest_off, uint32_t *key_idx,
+                            size_t *ndest) {
+    if (!r || !off || !dest || !dest_off || !key_idx || !ndest) return SWIMSIM_EINVAL;
+    *ndest = 0;
+    dest_off[0] = 0;
+    if (nkeys == 0) return SWIMSIM_OK;
+    if (!keys && off[nkeys]) return SWIMSIM_EINVAL;
+    if (!replica_dims_ok(nkeys, n)) return r->fail(SWIMSIM_EINVAL, "nkeys * n exceeds 2^31 - 1 entries");
+    if (n == 0) {
+        if (cnt) memset(cnt, 0, nkeys * sizeof *cnt);
+        return SWIMSIM_OK;
+    }
+    if (int rc = lookup_n_device(r, keys, off, nkeys, n)) return rc;
+    // sort (owner << 32 | key index) over the matrix, padding last; a destination starts where the owner changes
+    const size_t total = nkeys * n;
+    if (int rc = ensure_scratch(r, total)) return rc;
+    if (!r->nsel) RCHK(r, hipMalloc(&r->nsel, 16));
+    int idbits = 0;
+    while (((size_t)1 << idbits) < r->names.size()) idbits++;     // ids < 2^idbits; one more bit orders the padding
+    const int end_bit = std::min(64, 32 + idbits + 1);
+    size_t tb = 0, tb2 = 0;
+    hipcub::DeviceRadixSort::SortKeys(nullptr, tb, r->k0, r->k1, (int)total, 0, end_bit, r->s);
+    hipcub::DeviceSelect::Flagged(nullptr, tb2, r->kept, r->flag, r->k0, r->nsel, (int)total, r->s);
+    if (int rc = ensure_cub(r, std::max(tb, tb2))) return rc;
+    RCHK(r, hipEventRecord(r->e0, r->s));
+    hipLaunchKernelGGL(k_group_keys, dim3(grid_for(total)), dim3(256), 0, r->s, r->mat, n, (uint64_t)total, r->k0);
+    RCHK(r, hipcub::DeviceRadixSort::SortKeys(r->cub, tb, r->k0, r->k1, (int)total, 0, end_bit, r->s));
+    hipLaunchKernelGGL(k_group_bounds, dim3(grid_for(total)), dim3(256), 0, r->s, r->k1, (uint64_t)total, r->v0, r->flag,
+                       r->kept);
+    RCHK(r, hipcub::DeviceSelect::Flagged(r->cub, tb2, r->kept, r->flag, r->k0, r->nsel, (int)total, r->s));
+    RCHK(r, hipEventRecord(r->e1, r->s));
+    uint32_t nb = 0;
+    RCHK(r, hipMemcpyAsync(&nb, r->nsel, 4, hipMemcpyDeviceToHost, r->s));
+    RCHK(r, hipStreamSynchronize(r->s));
+    float ms = 0;
+    hipEventElapsedTime(&ms, r->e0, r->e1);
+    r->t_group = ms;
+    std::vector<unsigned long long> b(nb);
+    if (nb) RCHK(r, hipMemcpyAsync(b.data(), r->k0, (size_t)nb * 8, hipMemcpyDeviceToHost, r->s));
+    RCHK(r, hipStreamSynchronize(r->s));
+    size_t nd = nb, valid = total;
+    if (nb && (uint32_t)(b[nb - 1] >> 32) == 0xffffffffu) {       // the padding's run
+        nd = nb - 1;
+        valid = (uint32_t)b[nb - 1];
+    }
+    if (nd > r->nset) return r->fail(SWIMSIM_EHIP, "grouping found %zu destinations for %u servers", nd, r->nset);
+    for (size_t d = 0; d < nd; d++) {
+        dest[d] = (int32_t)(b[d] >> 32);
+        dest_off[d] = (uint32_t)b[d];
+    }
+    dest_off[nd] = valid;
+    *ndest = nd;
+    if (valid) RCHK(r, hipMemcpyAsync(key_idx, r->v0, valid * 4, hipMemcpyDeviceToHost, r->s));
+    if (out) RCHK(r, hipMemcpyAsync(out, r->mat, total * 4, hipMemcpyDeviceToHost, r->s));
+    if (cnt) RCHK(r, hipMemcpyAsync(cnt, r->uout, nkeys * 4, hipMemcpyDeviceToHost, r->s));
+    RCHK(r, hipStreamSynchronize(r->s));
+    return SWIMSIM_OK;
+}
+
+int swimring_last_replica_times(swimring_t *r, double *lookup_n_ms, double *group_ms) {
+    if (!r) return SWIMSIM_EINVAL;
+    if (lookup_n_ms) *lookup_n_ms = r->t_lookn;
+    if (group_ms) *group_ms = r->t_group;
     return SWIMSIM_OK;
 }
 

@@ -1,7 +1,8 @@
 """HashRing: the consistent-hash ring Ringpop feeds from swim's applied changes, on the MI355X
 (include/swimring.h, csrc/swimring.hip). The method names and meanings follow hashring.HashRing
 (hashring/hashring.go): AddServer / RemoveServer / AddRemoveServers / Checksum / HasServer /
-ServerCount / Servers / Lookup / LookupN. There is no CPU path: the ring lives in HBM and every
+ServerCount / Servers / Lookup / LookupN, plus LookupN for a batch of keys and the replica layer's
+groupReplicas (replica/replicator.go:170-191) over it. There is no CPU path: the ring lives in HBM and every
 hash, rebuild and lookup runs as a HIP kernel of libswimsim.so.
 """
 from __future__ import annotations
@@ -34,6 +35,9 @@ def _lib():
             "swimring_points": (C.c_int, [P, P, P, sz, C.POINTER(sz)]),
             "swimring_fingerprint32_batch": (C.c_int, [P, P, P, sz, P]),
             "swimring_last_times": (C.c_int, [P, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+            "swimring_lookup_n_batch": (C.c_int, [P, P, P, sz, u32, P, P]),
+            "swimring_group_replicas": (C.c_int, [P, P, P, sz, u32, P, P, P, P, P, C.POINTER(sz)]),
+            "swimring_last_replica_times": (C.c_int, [P, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
         }
         for name, (res, args) in sigs.items():
             f = getattr(L, name)
@@ -145,6 +149,59 @@ class HashRing:
 
     def servers(self):
         return self.lookup_n(b"", self.server_count())
+
+    # ---- LookupN for a batch, groupReplicas (replica/replicator.go:170-191) ----
+    def lookup_n_ids(self, keys, n: int):
+        """LookupN for a batch of keys in one launch: (ids int32[K, n], cnt uint32[K]). Row k holds key k's
+        cnt[k] owner ids in ring-walk order, then -1."""
+        blob, off = _pack(keys)
+        K = len(keys)
+        buf = np.full(max(1, K * n), -1, np.int32)
+        cnt = np.zeros(max(1, K), np.uint32)
+        self._chk(_lib().swimring_lookup_n_batch(self.h, blob, off.ctypes.data, K, n, buf.ctypes.data, cnt.ctypes.data))
+        return buf[:K * n].reshape(K, n), cnt[:K]
+
+    def _names_of(self, ids):
+        return {int(i): self.name(int(i)) for i in np.unique(ids) if i >= 0}
+
+    def lookup_n_batch(self, keys, n: int):
+        """LookupN per key: a list of owner-name lists (the preference lists, in ring-walk order)."""
+        ids, cnt = self.lookup_n_ids(keys, n)
+        nm = self._names_of(ids)
+        return [[nm[int(i)] for i in ids[k, :cnt[k]]] for k in range(len(keys))]
+
+    def group_replica_ids(self, keys, n: int):
+        """groupReplicas on the device, as arrays: (ids int32[K, n], cnt uint32[K], dest int32[D] ascending,
+        dest_off uint64[D + 1], key_idx uint32[dest_off[D]]): destination dest[d] owns the keys
+        key_idx[dest_off[d]:dest_off[d + 1]]."""
+        blob, off = _pack(keys)
+        K = len(keys)
+        ns = self.server_count()
+        buf = np.full(max(1, K * n), -1, np.int32)
+        cnt = np.zeros(max(1, K), np.uint32)
+        dest = np.empty(max(1, ns), np.int32)
+        doff = np.zeros(ns + 1, np.uint64)
+        kidx = np.empty(max(1, K * min(n, ns)), np.uint32)
+        nd = C.c_size_t(0)
+        self._chk(_lib().swimring_group_replicas(self.h, blob, off.ctypes.data, K, n, buf.ctypes.data, cnt.ctypes.data,
+                                                 dest.ctypes.data, doff.ctypes.data, kidx.ctypes.data, C.byref(nd)))
+        D = nd.value
+        return buf[:K * n].reshape(K, n), cnt[:K], dest[:D], doff[:D + 1], kidx[:int(doff[D])]
+
+    def group_replicas(self, keys, n: int):
+        """replicator.groupReplicas: (dests_by_key {key index: [names]}, keys_by_dest {name: [key indices]})."""
+        ids, cnt, dest, doff, kidx = self.group_replica_ids(keys, n)
+        nm = self._names_of(ids)
+        by_key = {k: [nm[int(i)] for i in ids[k, :cnt[k]]] for k in range(len(keys))}
+        by_dest = {self.name(int(dest[d])): [int(k) for k in kidx[int(doff[d]):int(doff[d + 1])]]
+                   for d in range(len(dest))}
+        return by_key, by_dest
+
+    def last_replica_times(self):
+        """(ms of the last batched LookupN kernel, ms of the last grouping: sort + boundaries)"""
+        a, b = C.c_double(), C.c_double()
+        self._chk(_lib().swimring_last_replica_times(self.h, C.byref(a), C.byref(b)))
+        return a.value, b.value
 
     def points(self):
         n = C.c_size_t()
