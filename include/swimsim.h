@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define SWIMSIM_ABI_VERSION 6
+#define SWIMSIM_ABI_VERSION 7
 
 enum {
     SWIMSIM_OK = 0,
@@ -35,7 +35,7 @@ enum {
     SWIMSIM_ENOMEM = -2,     /* device allocation failed */
     SWIMSIM_EHIP = -3,       /* HIP runtime error */
     SWIMSIM_ECAPACITY = -4,  /* a device pool overflowed (message / dense-snapshot pool) */
-    SWIMSIM_ERANGE = -5      /* incarnation not representable as t0 + e*period */
+    SWIMSIM_ERANGE = -5      /* incarnation not representable as t0 + e*period; clock offset out of range */
 };
 
 enum { SWIMSIM_ALIVE = 0, SWIMSIM_SUSPECT = 1, SWIMSIM_FAULTY = 2, SWIMSIM_LEAVE = 3, SWIMSIM_TOMBSTONE = 4,
@@ -113,7 +113,11 @@ enum {
     SWIMSIM_EV_LEAVE = 4,       /* adminLeaveHandler (handlers.go:145-148) */
     SWIMSIM_EV_PARTITION = 5,   /* set partition label of member a to b */
     SWIMSIM_EV_HEAL = 6,        /* discoverProviderHealer.Heal on observer a (heal_via_discover_provider.go:120) */
-    SWIMSIM_EV_REAP = 7         /* reapFaultyMembersHandler on observer a (handlers.go:154-163) */
+    SWIMSIM_EV_REAP = 7,        /* reapFaultyMembersHandler on observer a (handlers.go:154-163) */
+    SWIMSIM_EV_CLOCK = 8        /* observer a's clock offset becomes b periods (swimsim_set_clock_offset inside a
+                                   multi-round step; ABI 7). In list order: a later reincarnate, revive or leave of a in
+                                   the same round runs on the new clock. swimsim_step checks the clock events of its
+                                   rounds before it runs any (SWIMSIM_ERANGE, SWIMSIM_EINVAL; no round advanced) */
 };
 typedef struct swimsim_event { uint32_t round; uint32_t kind; int32_t a; int32_t b; } swimsim_event;
 
@@ -157,7 +161,29 @@ int swimsim_add_join_list(swimsim_t *h, uint32_t observer, const int32_t *member
                           uint32_t *applied);
 int swimsim_set_live(swimsim_t *h, uint32_t member, int32_t live);
 int swimsim_set_partition(swimsim_t *h, uint32_t member, int32_t label);
+/* SWIMSIM_ERANGE when a clock offset in force (below) would put a node's clock before t0 at that round */
 int swimsim_set_round(swimsim_t *h, uint32_t round);
+
+/* ---- per-node clocks (ABI 7): swim.Options.Clock (node.go:45-100, 194-238), one clock per swim.Node ----
+ * Observer o's clock in round r is now(o) = t0 + (r + k_o) * period; k_o (signed, whole periods, 0 at create) is
+ * its offset: a skewed or stepped clock, as the reference's partition-heal tests give their two partitions
+ * (heal_partition_test.go:447-454). The clock enters where the reference reads it: a refute's and Reincarnate's
+ * incarnation (memberlist.go:337-354, 234-236) and the timer deadlines (state_transitions.go:119-160). Incarnations
+ * and deadlines are absolute values in the owner's clock, so a change of k_o rewrites nothing: after a forward step
+ * every timer with deadline <= now(o) fires in the next phase T, in (deadline, member) order, each with now =
+ * deadline; after a backward step timers wait longer, and a refute or Reincarnate may write an incarnation below the
+ * one held before (the node then loses to the rumour it refutes until its clock passes it). With every offset 0
+ * results are bit-identical to a handle that never set one. Random streams, iterator epochs and counters stay on
+ * the round.
+ * Errors, before any state changes: SWIMSIM_EINVAL (NULL handle or pointer, observer >= N); SWIMSIM_ERANGE when
+ * offset_ms is not a multiple of the period (the engine stores e), when |offset| > 32,767 periods (one step stays
+ * below the lateness field of the per-Update stream's timer tags), or when round + k_o < 0 (a clock before t0).
+ * Shards: like swimsim_set_live, every shard of a cluster takes the same calls and keeps the whole table. */
+int swimsim_set_clock_offset(swimsim_t *h, uint32_t observer, int64_t offset_ms);
+/* every offset with one upload: offset_ms[N] */
+int swimsim_set_clock_offsets(swimsim_t *h, const int64_t *offset_ms);
+/* the offsets in force, in ms: out[N] */
+int swimsim_clock_offsets(swimsim_t *h, int64_t *out);
 
 /* ---- the hot path: nrounds protocol periods of every live node (gossip.ProtocolPeriod,
  *      gossip.go:178-188, for all N nodes under docs/ROUND_SEMANTICS.md). events are applied

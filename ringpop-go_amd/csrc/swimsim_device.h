@@ -91,6 +91,9 @@ struct DS {
     uint32_t *tblk;
     uint8_t *live;
     int32_t *part;
+    int32_t *coff;          // [N] clock offset k_o of each observer, in periods: observer o's clock in round r is
+                            // r + coff[o] (docs/ROUND_SEMANTICS.md §2). Indexed by global observer like live; zero at
+                            // create. A row's incarnations and timer deadlines are absolute values in its own clock.
     const uint32_t *addrw;  // [N][6]
     const uint32_t *tailw;  // [ecap*4][8]: tail bytes status‖digits‖';' as words, word 6 = tail length
     const uint32_t *rtail;  // [ecap*4][8]: record bytes [4*(W/4), 4*(W/4) + 28) of addr‖tail with the
@@ -188,6 +191,12 @@ constexpr uint32_t SRC_PEND = 0x7FFFFFFEu, SRC_CLAIM = 0x7FFFFFFDu;
 __device__ __forceinline__ uint32_t hot_slot(const DS &d, uint32_t m) { return d.hidx ? d.hidx[m] : SRC_NONE; }
 
 __host__ __device__ inline bool is_pingable(uint32_t st) { return st <= ST_SUSPECT; }
+
+// observer o's clock in round r, in periods since t0: now(o) = t0 + (r + k_o) * period. The host keeps r + k_o >= 0
+// (swimsim_set_clock_offset, swimsim_set_round), so the unsigned sum is exact. Everything that is a node's clock (a
+// refute's or Reincarnate's incarnation, timer deadlines and their expiry) takes this; Philox streams, iterator
+// epochs and counters stay on the round.
+__device__ __forceinline__ uint32_t clock_of(const DS &d, uint32_t o, uint32_t r) { return r + (uint32_t)d.coff[o]; }
 
 // A change record in the message pool is 16 B: {member | status << 24 | tag_lo << 27, e | tag_hi << 24, source,
 // source e} (e < 2^24: ensure_ecap). The 13-bit tag carries the member's hot slot in the receiving handle,

@@ -305,6 +305,9 @@ struct swimsim {
     // host mirrors
     std::vector<uint8_t> live;
     std::vector<int32_t> part;
+    std::vector<int32_t> coff;                // [N] clock offsets in periods (DS::coff), every shard the whole table
+    int32_t coff_min = 0, coff_max = 0;       // their range (0 included): round + coff_min >= 0 always holds, and the
+                                              // checksum tables cover incarnation round + coff_max + 1 (ensure_ecap)
     std::vector<std::string> addrs;
     uint32_t round = 0;
     uint64_t host_ctr[SWIMSIM_NCOUNTERS] = {0};
@@ -1336,6 +1339,15 @@ int run_waves(swimsim *h, int phase, uint32_t nruns_valid, uint32_t maxcount) {
     return 0;
 }
 
+// the range of the clock offsets in force (after a setter or a clock event changed h->coff)
+void clock_offset_range(swimsim *h) {
+    h->coff_min = h->coff_max = 0;
+    for (int32_t k : h->coff) {
+        h->coff_min = std::min(h->coff_min, k);
+        h->coff_max = std::max(h->coff_max, k);
+    }
+}
+
 int flush_events(swimsim *h, std::vector<uint4> &evs) {
     if (evs.empty()) return 0;
     Scope sc(h, F_EVENTS);
@@ -1520,6 +1532,14 @@ int step_one(swimsim *h, const swimsim_event *ev, size_t nev) {
         case SWIMSIM_EV_LEAVE: if (h->live[a] && own(h, a)) batch.push_back(make_uint4(3, a, a, 0)); break;
         case SWIMSIM_EV_PARTITION: h->part[a] = e.b; topo_dirty = true; break;
         case SWIMSIM_EV_REAP: if (h->live[a] && own(h, a)) batch.push_back(make_uint4(4, a, a, 0)); break;
+        case SWIMSIM_EV_CLOCK:
+            // a's clock steps to round + b periods (validated for the whole call by swimsim_step). Every shard
+            // keeps the whole table, so the entry goes into every shard's batch: k_events writes it in list order,
+            // before a later Reincarnate, revive or leave of a in this round, and a heal flushes the batch first
+            h->coff[a] = e.b;
+            clock_offset_range(h);
+            batch.push_back(make_uint4(5, a, a, (uint32_t)e.b));
+            break;
         case SWIMSIM_EV_HEAL:
             if (!h->live[a]) break;
             if (int rc = flush_events(h, batch)) return rc;
@@ -1691,6 +1711,31 @@ int to_e(swimsim *h, int64_t inc_ms, uint32_t *e) {
 
 inline int64_t from_e(const swimsim *h, uint32_t e) { return h->t0 + (int64_t)e * h->period; }
 
+// ---- per-observer clock offsets (docs/ROUND_SEMANTICS.md §2 Clock; swim.Options.Clock, node.go) ----
+// One clock step stays below the 65,535-period lateness field of k_timers' event tags, so the per-Update stream keeps
+// the exact (deadline, member) order of the timers a step makes due at once: |k| <= 32,767.
+constexpr int64_t kMaxClockOffset = 32767;
+
+// offset k (periods) of one observer at round `round`: in range, and the clock not before t0 (the row words hold e
+// unsigned)
+int check_clock_offset(swimsim *h, uint32_t o, int64_t k, uint32_t round) {
+    if (k > kMaxClockOffset || k < -kMaxClockOffset)
+        return h->fail(SWIMSIM_ERANGE, "clock offset of observer %u: %lld periods (at most %lld either way)", o, (long long)k,
+                       (long long)kMaxClockOffset);
+    if ((int64_t)round + k < 0)
+        return h->fail(SWIMSIM_ERANGE, "clock offset of observer %u: %lld periods at round %u puts its clock before t0", o,
+                       (long long)k, round);
+    return 0;
+}
+
+int clock_offset_periods(swimsim *h, uint32_t o, int64_t offset_ms, int64_t *k) {
+    if (offset_ms % (int64_t)h->period)
+        return h->fail(SWIMSIM_ERANGE, "clock offset of observer %u: %lld ms is not a multiple of the period (%u ms)", o,
+                       (long long)offset_ms, h->period);
+    *k = offset_ms / (int64_t)h->period;
+    return 0;
+}
+
 // canonical split of N observer rows over G shards: shard r holds [N*r/G, N*(r+1)/G)
 std::vector<uint32_t> canonical_split(uint32_t N, uint32_t G) {
     std::vector<uint32_t> lo(G + 1);
@@ -1852,6 +1897,7 @@ int swimsim_create(const swimsim_config *cfg, swimsim_t **out) {
         (rc = dalloc(h, &d.njobs, h->NL, "njobs")) || (rc = dalloc(h, &d.jobs, (size_t)h->NL * h->maxjobs, "jobs")) ||
         (rc = dalloc(h, &d.dbit, (size_t)h->NL * d.NBIT, "dbit")) || (rc = dalloc(h, &d.tblk, (size_t)h->NL * d.NB, "tblk")) ||
         (rc = dalloc(h, &d.live, h->N, "live")) || (rc = dalloc(h, &d.part, h->N, "part")) ||
+        (rc = dalloc(h, &d.coff, h->N, "clock offsets")) ||
         (rc = dalloc(h, &d.ctr, (size_t)CTR_SHARDS * CTR_STRIDE, "counters")) || (rc = dalloc(h, &d.err, 4, "err")) ||
         (rc = dalloc(h, &d.clen, h->NL, "clen")) || (rc = dalloc(h, &d.clast, h->NL, "clast")) ||
         (rc = dalloc(h, &d.cpslot, h->NL, "cpslot")) || (rc = dalloc(h, &d.nhe, h->NL, "cold entry counts")) ||
@@ -1860,6 +1906,8 @@ int swimsim_create(const swimsim_config *cfg, swimsim_t **out) {
         (rc = dalloc(h, &d.ucnt, 2, "divergent column counts")))
         return bail(rc);
     hipMemset(d.nhe, 0, (size_t)h->NL * 4);
+    hipMemset(d.coff, 0, (size_t)h->N * 4);                        // every node on the round clock
+    h->coff.assign(h->N, 0);
     hipMemset(d.colx, 0xFF, (size_t)d.NBIT * 4);
     hipMemset(d.cpslot, 0xFF, (size_t)h->NL * 4);
     {
@@ -2162,7 +2210,7 @@ int swimsim_add_join_list(swimsim_t *h, uint32_t o, const int32_t *member, const
         emax = std::max(emax, e);
         rec[i] = make_uint4((uint32_t)m | ((uint32_t)st << 24), e, src, se);
     }
-    if (int rc = ensure_ecap(h, std::max(emax, h->round) + 1)) return rc;
+    if (int rc = ensure_ecap(h, std::max(emax, h->round + (uint32_t)h->coff_max) + 1)) return rc;
     if (!h->jl)
         if (int rc = dalloc(h, &h->jl, h->N, "join list")) return rc;
     uint32_t napp = 0;
@@ -2191,13 +2239,64 @@ int swimsim_set_partition(swimsim_t *h, uint32_t m, int32_t label) {
 
 int swimsim_set_round(swimsim_t *h, uint32_t r) {
     if (!h) return SWIMSIM_EINVAL;
+    if ((int64_t)r + h->coff_min < 0)                              // (as the offset setters check: no clock before t0)
+        return h->fail(SWIMSIM_ERANGE, "round %u puts a clock before t0 (an offset of %d periods is in force)", r, h->coff_min);
     h->round = r;
-    return ensure_ecap(h, r + 1);
+    return ensure_ecap(h, r + (uint32_t)h->coff_max + 1);
+}
+
+// ---- per-observer clocks: swim.Options.Clock (node.go) of each simulated node ----
+int swimsim_set_clock_offset(swimsim_t *h, uint32_t o, int64_t offset_ms) {
+    if (!h || o >= h->N) return SWIMSIM_EINVAL;
+    int64_t k = 0;
+    if (int rc = clock_offset_periods(h, o, offset_ms, &k)) return rc;
+    if (int rc = check_clock_offset(h, o, k, h->round)) return rc;
+    if (int rc = ensure_ecap(h, h->round + (uint32_t)std::max<int64_t>(k, h->coff_max) + 1)) return rc;
+    h->coff[o] = (int32_t)k;
+    clock_offset_range(h);
+    HIPCHK(h, hipMemcpyAsync(h->d.coff + o, &h->coff[o], 4, hipMemcpyHostToDevice, h->s));
+    HIPCHK(h, stream_sync(h));
+    return SWIMSIM_OK;
+}
+
+int swimsim_set_clock_offsets(swimsim_t *h, const int64_t *offset_ms) {
+    if (!h || !offset_ms) return SWIMSIM_EINVAL;
+    std::vector<int32_t> ks(h->N);
+    int64_t kmax = 0;
+    for (uint32_t o = 0; o < h->N; o++) {
+        int64_t k = 0;
+        if (int rc = clock_offset_periods(h, o, offset_ms[o], &k)) return rc;
+        if (int rc = check_clock_offset(h, o, k, h->round)) return rc;
+        ks[o] = (int32_t)k;
+        kmax = std::max(kmax, k);
+    }
+    if (int rc = ensure_ecap(h, h->round + (uint32_t)kmax + 1)) return rc;
+    h->coff.swap(ks);
+    clock_offset_range(h);
+    HIPCHK(h, hipMemcpyAsync(h->d.coff, h->coff.data(), (size_t)h->N * 4, hipMemcpyHostToDevice, h->s));
+    HIPCHK(h, stream_sync(h));
+    return SWIMSIM_OK;
+}
+
+int swimsim_clock_offsets(swimsim_t *h, int64_t *out) {
+    if (!h || !out) return SWIMSIM_EINVAL;
+    for (uint32_t o = 0; o < h->N; o++) out[o] = (int64_t)h->coff[o] * (int64_t)h->period;
+    return SWIMSIM_OK;
 }
 
 int swimsim_step(swimsim_t *h, uint32_t nrounds, const swimsim_event *events, size_t nevents) {
     if (!h) return SWIMSIM_EINVAL;
     if (h->G == 1 && h->NL != h->N) return h->fail(SWIMSIM_EINVAL, "a partial observer range needs a shard transport");
+    // the clock events of the rounds this call runs, checked before any round runs (so a bad one changes nothing),
+    // and the largest offset they set (the checksum tables must cover it when its round begins)
+    int32_t ev_kmax = 0;
+    for (size_t i = 0; i < nevents; i++) {
+        const swimsim_event &e = events[i];
+        if (e.kind != SWIMSIM_EV_CLOCK || e.round < h->round || e.round - h->round >= nrounds) continue;
+        if (e.a < 0 || (uint32_t)e.a >= h->N) return h->fail(SWIMSIM_EINVAL, "event member %d out of range", e.a);
+        if (int rc = check_clock_offset(h, (uint32_t)e.a, e.b, e.round)) return rc;
+        ev_kmax = std::max(ev_kmax, e.b);
+    }
     if (h->colx_stale && nrounds) {                                // (no snapshot is alive between step calls)
         // the rebuild reads the live rows only: every step call ends with the side stream drained, and dense snapshots
         // live within one round, so none can hold a word the rebuilt bitmap would not cover
@@ -2206,7 +2305,8 @@ int swimsim_step(swimsim_t *h, uint32_t nrounds, const swimsim_event *events, si
         h->colx_stale = false;
     }
     for (uint32_t i = 0; i < nrounds; i++) {
-        if (int rc = ensure_ecap(h, h->round + 1)) return rc;
+        // (a refute or Reincarnate of this round writes incarnation round + k_o at most)
+        if (int rc = ensure_ecap(h, h->round + (uint32_t)std::max(h->coff_max, ev_kmax) + 1)) return rc;
         if (int rc = step_one(h, events, nevents)) return rc;
     }
     if (int rc = sync_side(h)) return rc;    // a step call returns with every checksum current

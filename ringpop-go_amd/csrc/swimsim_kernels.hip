@@ -254,6 +254,9 @@ __device__ __forceinline__ uint32_t uni(uint32_t x) { return (uint32_t)__builtin
 __device__ __forceinline__ unsigned long long uni64(unsigned long long x) {
     return ((unsigned long long)uni((uint32_t)(x >> 32)) << 32) | uni((uint32_t)x);
 }
+// observer o's clock in round r for the wave that works on o's row (clock_of, wave-uniform: one load at kernel entry
+// beside the row scalars, then a scalar register for every merge of the launch)
+__device__ __forceinline__ uint32_t wave_clock(const DS &d, uint32_t o, uint32_t r) { return uni(clock_of(d, o, r)); }
 __device__ __forceinline__ RowPre row_pre(const DS &d, uint32_t ol) {
     RowPre p;
     p.nhe = (int32_t)uni((uint32_t)d.nhe[ol]); p.ping = (int32_t)uni((uint32_t)d.ping[ol]);
@@ -1053,6 +1056,7 @@ __global__ void k_hot_flush(DS d, uint32_t ol0, uint32_t nrows) {
 __global__ void k_add_join_list(DS d, uint32_t ol, const uint4 *__restrict__ rec, uint32_t n, uint32_t r,
                                 uint32_t *applied_out) {
     const uint32_t o = d.lo + ol;
+    const uint32_t now = wave_clock(d, o, r);
     const uint32_t *rowp = d.mw + (size_t)ol * d.NP;
     MAcc acc;
     acc_begin(d, ol, acc);
@@ -1071,7 +1075,7 @@ __global__ void k_add_join_list(DS d, uint32_t ol, const uint4 *__restrict__ rec
             if (c[u].x == 0xFFFFFFFFu) continue;
             const uint32_t m = c[u].x & 0xFFFFFFu;
             const int before = acc.napp;
-            merge_change_w(d, ol, o, m, cur[u], c[u].x >> 24, c[u].y, c[u].z, c[u].w, r, r, acc);
+            merge_change_w(d, ol, o, m, cur[u], c[u].x >> 24, c[u].y, c[u].z, c[u].w, now, now, acc);
             if (acc.napp != before && m != o) {                    // ClearChange(member)
                 const size_t idx = (size_t)ol * d.NP + m;
                 d.dent[idx].x = DE_NONE;
@@ -1092,12 +1096,12 @@ __global__ void k_add_join_list(DS d, uint32_t ol, const uint4 *__restrict__ rec
 // ---------------------------------------------------------------------------------------------
 // phase E: host events, applied in order by one thread (few per round)
 // ---------------------------------------------------------------------------------------------
-// returns the number of applied changes (0/1)
-__device__ int thread_make_change(const DS &d, uint32_t ol, uint32_t o, uint32_t m, uint32_t e, uint32_t st, uint32_t r) {
+// returns the number of applied changes (0/1); now = the observer's clock (clock_of)
+__device__ int thread_make_change(const DS &d, uint32_t ol, uint32_t o, uint32_t m, uint32_t e, uint32_t st, uint32_t now) {
     MAcc acc;
     acc_begin(d, ol, acc);
     const uint32_t self_e = d.mw[(size_t)ol * d.NP + o] >> 3;   // MakeChange: SourceIncarnation = local inc
-    merge_change(d, ol, o, m, st, e, o, self_e, r, r, acc);
+    merge_change(d, ol, o, m, st, e, o, self_e, now, now, acc);
     fold_row(d, ol, acc.dping, acc.ddc, acc.napp, acc.nref, 0, acc.dlen, acc.maxlast, acc.inval, acc.dfp, true, acc.dnh);
     return acc.napp;
 }
@@ -1107,23 +1111,29 @@ __global__ void k_events(DS d, const uint4 *ev, uint32_t nev, uint32_t r, uint32
     for (uint32_t i = 0; i < nev; i++) {
         const uint4 e = ev[i];   // {kind, observer, member, e | status << 29 | label}
         const uint32_t kind = e.x, o = e.y;
+        if (kind == 5) {         // clock step: k_o = e.w periods, on every shard (each keeps the whole table). In list
+            d.coff[o] = (int32_t)e.w;   // order: a later Reincarnate or leave of o in this batch runs on the new clock
+            if (applied_out) applied_out[i] = 0;
+            continue;
+        }
         if (o < d.lo || o >= d.lo + d.NL) continue;
         const uint32_t ol = o - d.lo;
+        const uint32_t now = clock_of(d, o, r);
         int applied = 0;
         switch (kind) {
         case 1:  // MakeChange(o, member, e, status)
-            applied = thread_make_change(d, ol, o, e.z, e.w & 0x1FFFFFFFu, e.w >> 29, r);
+            applied = thread_make_change(d, ol, o, e.z, e.w & 0x1FFFFFFFu, e.w >> 29, now);
             break;
         case 2:  // Reincarnate: MakeAlive(self, now) (memberlist.go:234-236)
-            applied = thread_make_change(d, ol, o, o, r, ST_ALIVE, r);
+            applied = thread_make_change(d, ol, o, o, now, ST_ALIVE, now);
             break;
         case 3:  // admin leave: MakeLeave(self, local inc) (handlers.go:145-148)
-            applied = thread_make_change(d, ol, o, o, d.mw[(size_t)ol * d.NP + o] >> 3, ST_LEAVE, r);
+            applied = thread_make_change(d, ol, o, o, d.mw[(size_t)ol * d.NP + o] >> 3, ST_LEAVE, now);
             break;
         case 4:  // reap: faulty → tombstone (handlers.go:154-163)
             for (uint32_t m = 0; m < d.N; m++) {
                 const uint32_t w = d.mw[(size_t)ol * d.NP + m];
-                if ((w & 7u) == ST_FAULTY) applied += thread_make_change(d, ol, o, m, w >> 3, ST_TOMB, r);
+                if ((w & 7u) == ST_FAULTY) applied += thread_make_change(d, ol, o, m, w >> 3, ST_TOMB, now);
             }
             break;
         }
@@ -1132,13 +1142,16 @@ __global__ void k_events(DS d, const uint4 *ev, uint32_t nev, uint32_t r, uint32
 }
 
 // ---------------------------------------------------------------------------------------------
-// phase T: timers (state_transitions.go:90-160 on the round clock; Mock.Add fires in deadline
-// order with now = deadline, so a follow-up schedule is based at the fired deadline)
+// phase T: timers (state_transitions.go:90-160 on the observer's clock; Mock.Add fires in deadline
+// order with now = deadline, so a follow-up schedule is based at the fired deadline). After a forward
+// clock step every deadline the step passed is due at once: all fire in this launch, still in
+// (deadline, member) order; a follow-up timer that is already due as well fires in the next round.
 // ---------------------------------------------------------------------------------------------
-__global__ void k_timers(DS d, uint32_t r) {
+__global__ void k_timers(DS d, uint32_t round) {
     const uint32_t ol = wave_gid();
     if (ol >= d.NL) return;
     const uint32_t o = d.lo + ol;
+    const uint32_t r = wave_clock(d, o, round);      // deadlines are values of o's own clock
     if (!d.live[o] || d.tmin[ol] > r) return;
     const uint32_t self_e = d.mw[(size_t)ol * d.NP + o] >> 3;
     MAcc acc;
@@ -1489,7 +1502,7 @@ __global__ void k_pair_info(const DS d, const uint32_t *vals, uint32_t n, int ph
 // heal rounds did, sharded): a dense message, or a bound above 4,096 records or a sixteenth of a sub-pool, allocates
 // the exact count after the merge (at most 4,096 spare records per receiver).
 __device__ __forceinline__ void recv_one_pre(const DS &d, const RecvArgs &a, uint32_t j, const uint4 pi0, const uint4 pi1,
-                                             uint32_t pair, uint32_t nslots, RowPre &p, LazyCtx &lz) {
+                                             uint32_t pair, uint32_t nslots, uint32_t now, RowPre &p, LazyCtx &lz) {
     const uint32_t ol = j - d.lo;
     const uint32_t v = pi1.w, sender = a.phase == 0 ? v : v / d.K, resp_idx = v;
     MsgDesc md;
@@ -1498,7 +1511,7 @@ __device__ __forceinline__ void recv_one_pre(const DS &d, const RecvArgs &a, uin
     const bool early = md.kind == 0 && bound > 0 && bound <= min(4096ull, d.pool_cap / POOL_SHARDS / 16);
     unsigned long long roff = 0;
     if (early && lane_id() == 0) roff = pool_alloc_lane0(d, (uint32_t)bound);   // (read after the merge)
-    wave_merge_msg_pre(d, ol, j, md, a.r, a.r, 0, p, -1, nullptr, true, &lz);
+    wave_merge_msg_pre(d, ol, j, md, now, now, 0, p, -1, nullptr, true, &lz);
     MsgDesc resp;
     resp.kind = 0; resp.len = 0; resp.off_lo = resp.off_hi = 0;
     uint32_t kept = 0;
@@ -1570,13 +1583,14 @@ __global__ void __launch_bounds__(256, RECV_MIN_WAVES) k_recv(DS d, RecvArgs a) 
     if (key >= d.N) return;
     const uint32_t n = a.counts[u], off = a.offs[u];
     RowPre p = row_pre(d, key - d.lo);
+    const uint32_t now = wave_clock(d, key, a.r);                  // the receiver's clock: refutes, timer schedules
     const uint32_t nslots = d.hidx ? d.hot_cnt[0] : 0u;
     LazyCtx lz;
     lz.sS = a.sS; lz.sI = a.sI;
     lz.pend = a.sS && d.ulog && uni(a.sS[key]) == SRC_PEND;        // this row is a pending-live sender of the phase
     for (uint32_t w = 0; w < n; w++) {
         const uint32_t pair = off + w;
-        recv_one_pre(d, a, key, a.pinfo[2 * (size_t)pair], a.pinfo[2 * (size_t)pair + 1], pair, nslots, p, lz);
+        recv_one_pre(d, a, key, a.pinfo[2 * (size_t)pair], a.pinfo[2 * (size_t)pair + 1], pair, nslots, now, p, lz);
     }
     if (d.ulog_cnt && lane_id() == 0) d.ulog_cnt[key - d.lo] = min(p.ulog, d.ulog_cap + 1u);
 }
@@ -1949,11 +1963,12 @@ __global__ void k_resp(DS d, const int32_t *tgt, const uint8_t *failed, const Ms
     const uint32_t o = d.lo + ol;
     // (the row scalars, both descriptors: one round trip; RowPre carries them through the bump and the merge)
     RowPre p = row_pre(d, ol);
+    const uint32_t now = wave_clock(d, o, r);
     const MsgDesc sd = sdesc[o], rd = rdesc[o];
     uint4 rec0[MB];                                                 // (the response's first records ride with the bump's
     merge_first(d, rd, rec0);                                       // loads: the pool is read-only here)
     wave_bump_pre(d, ol, sd, p);
-    wave_merge_msg_pre(d, ol, o, rd, r, r, 1, p, C_X_DENSE_RESP, rec0);
+    wave_merge_msg_pre(d, ol, o, rd, now, now, 1, p, C_X_DENSE_RESP, rec0);
     if (lane_id() == 0) {
         ctr_add(d, C_PINGS_OK, 1ull);
         if (sd.kind == 0) ctr_add(d, C_X_BUMPED, (unsigned long long)sd.len);
@@ -1966,6 +1981,7 @@ __global__ void k_resolve(DS d, const int32_t *tgt, const uint8_t *failed, const
     const uint32_t ol = wave_gid();
     if (ol >= d.NL || !failed[ol]) return;
     const uint32_t o = d.lo + ol, K = d.K;
+    const uint32_t now = wave_clock(d, o, r);
     uint32_t errs = 0;
     for (uint32_t q = 0; q < nh[ol]; q++) {
         const uint32_t h = H[(size_t)ol * K + q];
@@ -1973,7 +1989,7 @@ __global__ void k_resolve(DS d, const int32_t *tgt, const uint8_t *failed, const
             errs++;
             wave_bump(d, ol, sdesc2[o]);                            // bump only on error (105-106)
         } else {
-            wave_merge_msg(d, ol, o, rdesc2[(size_t)o * K + q], r, r, 2, C_X_DENSE_RESP);
+            wave_merge_msg(d, ol, o, rdesc2[(size_t)o * K + q], now, now, 2, C_X_DENSE_RESP);
         }
     }
     if (lane_id() == 0) {
@@ -1984,7 +2000,7 @@ __global__ void k_resolve(DS d, const int32_t *tgt, const uint8_t *failed, const
             ctr_add(d, C_SUSPECT_DECL, 1ull);
             const uint32_t t = (uint32_t)tgt[ol];
             const uint32_t te = d.mw[(size_t)ol * d.NP + t] >> 3;      // member.Incarnation read now (node.go:508)
-            thread_make_change(d, ol, o, t, te, ST_SUSPECT, r);
+            thread_make_change(d, ol, o, t, te, ST_SUSPECT, now);
         }
     }
 }
@@ -2012,9 +2028,11 @@ __global__ void k_jobs_merge(DS d, const MsgDesc *snapdesc, uint32_t r) {
     const uint32_t ol = wave_gid();
     if (ol >= d.NL) return;
     const uint32_t nj = d.njobs[ol];
+    if (!nj) return;
+    const uint32_t now = wave_clock(d, d.lo + ol, r);
     for (uint32_t q = 0; q < nj; q++) {
         const uint32_t src = d.jobs[(size_t)ol * d.maxjobs + q];
-        wave_merge_msg(d, ol, d.lo + ol, snapdesc[src], r, r, 3, C_X_DENSE_JOBS);
+        wave_merge_msg(d, ol, d.lo + ol, snapdesc[src], now, now, 3, C_X_DENSE_JOBS);
     }
     if (lane_id() == 0 && nj) ctr_add(d, C_RFS_DONE, (unsigned long long)nj);
 }
@@ -2286,7 +2304,8 @@ __global__ void k_sender_info(DS d, uint32_t ol, uint32_t *out) {
 }
 
 __global__ void k_apply_msg(DS d, uint32_t ol, const MsgDesc *md, uint32_t r) {
-    wave_merge_msg(d, ol, d.lo + ol, *md, r, r, 2, C_X_DENSE_HEAL);
+    const uint32_t now = wave_clock(d, d.lo + ol, r);
+    wave_merge_msg(d, ol, d.lo + ol, *md, now, now, 2, C_X_DENSE_HEAL);
 }
 
 // sendPingWithChanges o → t whose response is discarded (heal_partition.go:97-124): target runs
@@ -2294,7 +2313,8 @@ __global__ void k_apply_msg(DS d, uint32_t ol, const MsgDesc *md, uint32_t r) {
 __global__ void k_ping_with(DS d, uint32_t tol, uint32_t sender, const MsgDesc *md, const uint32_t *sics,
                             MsgDesc *resp_out, uint4 *defer, uint32_t *defer_cnt, uint32_t r) {
     const uint32_t sinc = sics[0], scs = sics[1];
-    wave_merge_msg(d, tol, d.lo + tol, *md, r, r, 2);
+    const uint32_t now = wave_clock(d, d.lo + tol, r);            // the target's clock (it runs the Update)
+    wave_merge_msg(d, tol, d.lo + tol, *md, now, now, 2);
     MsgDesc resp;
     const uint32_t kept = wave_issue_recv(d, tol, sender, sinc, resp);
     if (kept == 0) {

@@ -28,6 +28,7 @@ ALIVE, SUSPECT, FAULTY, LEAVE, TOMBSTONE, UNKNOWN = 0, 1, 2, 3, 4, 7
 STATUS_NAMES = {ALIVE: "alive", SUSPECT: "suspect", FAULTY: "faulty", LEAVE: "leave", TOMBSTONE: "tombstone"}
 SOURCE_NONE = -1
 EV_KILL, EV_REVIVE, EV_REINCARNATE, EV_LEAVE, EV_PARTITION, EV_HEAL, EV_REAP = 1, 2, 3, 4, 5, 6, 7
+EV_CLOCK = 8                                     # (r, EV_CLOCK, observer, offset in periods): a clock step mid-run
 COUNTER_NAMES = [
     "rounds", "pings", "pings_ok", "pingreqs", "helper_calls", "helper_errors", "inconclusive",
     "suspect_decl", "applied", "refutes", "full_syncs", "full_syncs_pingreq", "rfs_done",
@@ -140,6 +141,9 @@ def load_library(path: str = LIB_PATH):
         "swimsim_set_live": (C.c_int, [P, u32, i32]),
         "swimsim_set_partition": (C.c_int, [P, u32, i32]),
         "swimsim_set_round": (C.c_int, [P, u32]),
+        "swimsim_set_clock_offset": (C.c_int, [P, u32, i64]),
+        "swimsim_set_clock_offsets": (C.c_int, [P, P]),
+        "swimsim_clock_offsets": (C.c_int, [P, P]),
         "swimsim_step": (C.c_int, [P, u32, C.POINTER(Event), sz]),
         "swimsim_heal": (C.c_int, [P, u32, P, sz, C.POINTER(sz)]),
         "swimsim_round": (u32, [P]),
@@ -442,6 +446,25 @@ class Cluster:
 
     def set_round(self, r):
         self._chk(load_library().swimsim_set_round(self.h, r))
+
+    # ---- per-node clocks (swim.Options.Clock, node.go): now(o) = t0 + round * period + offset_o ----
+    def set_clock_offset(self, o, offset_ms):
+        """observer o's clock offset in ms: a signed multiple of the period, at most 32,767 periods either way, and
+        never a clock before t0 (SwimsimError ERANGE otherwise, nothing changed)"""
+        self._chk(load_library().swimsim_set_clock_offset(self.h, o, int(offset_ms)))
+
+    def set_clock_offsets(self, offsets_ms):
+        """every observer's clock offset (length-n array of ms) with one upload"""
+        a = np.ascontiguousarray(offsets_ms, dtype=np.int64)
+        if a.shape != (self.n,):
+            raise ValueError(f"set_clock_offsets needs a length-{self.n} array")
+        self._chk(load_library().swimsim_set_clock_offsets(self.h, a.ctypes.data))
+
+    def clock_offsets(self):
+        """the clock offsets in force, in ms (length n)"""
+        out = np.empty(self.n, np.int64)
+        self._chk(load_library().swimsim_clock_offsets(self.h, out.ctypes.data))
+        return out
 
     # ---- read-back -------------------------------------------------------------------------
     def checksums(self):
@@ -772,6 +795,22 @@ class ShardedCluster:
     def set_partition(self, m, label):
         for c in self.shards:
             c.set_partition(m, label)
+
+    def set_round(self, r):
+        for c in self.shards:
+            c.set_round(r)
+
+    # per-node clocks: every shard takes the same calls and keeps the whole table (like set_live)
+    def set_clock_offset(self, o, offset_ms):
+        for c in self.shards:
+            c.set_clock_offset(o, offset_ms)
+
+    def set_clock_offsets(self, offsets_ms):
+        for c in self.shards:
+            c.set_clock_offsets(offsets_ms)
+
+    def clock_offsets(self):
+        return self.shards[0].clock_offsets()
 
 
 class MemberView:

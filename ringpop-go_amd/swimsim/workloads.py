@@ -9,6 +9,7 @@ from __future__ import annotations
 from dataclasses import dataclass, field
 
 EV_KILL, EV_REVIVE, EV_REINCARNATE, EV_LEAVE, EV_PARTITION, EV_HEAL, EV_REAP = 1, 2, 3, 4, 5, 6, 7
+EV_CLOCK = 8                                     # (r, EV_CLOCK, observer, offset in periods): a clock step mid-run
 M32 = 0xFFFFFFFF
 
 
