@@ -57,7 +57,11 @@ typedef struct swimsim_config {
     uint32_t p_factor;                 /* disseminator pFactor, default 15 (disseminator.go:35) */
     uint64_t seed;                     /* Philox key (docs/ROUND_SEMANTICS.md §6) */
     const char *addresses;             /* NULL: synthetic "10.%03u.%03u.%03u:7000"; else N fixed-width,
-                                          strictly ascending addresses, each addr_stride bytes */
+                                          strictly ascending addresses, each addr_stride bytes (shorter ones
+                                          NUL-padded). Widths of 13..20 bytes; any other width, unequal
+                                          widths or an address not above its predecessor: SWIMSIM_EINVAL. A
+                                          record tail status + decimal(t0 + e * period) + ';' of more than
+                                          24 bytes is refused the same way */
     uint32_t addr_stride;
     uint32_t max_rounds;               /* incarnation table capacity (default 65536 rounds) */
     uint64_t message_pool_bytes;       /* change-record pool; 0 = automatic */

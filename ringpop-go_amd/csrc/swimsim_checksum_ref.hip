@@ -295,6 +295,11 @@ __global__ void __launch_bounds__(256, CSD_SCAN_MINB) k_csd_scan(DS d, const uin
         int32_t khi = y >= 1 ? (y - 1) / 20 : -1;
         if (khi > (int32_t)kl) khi = (int32_t)kl;
         const bool vd = dl && klo <= (int32_t)kl && khi >= klo;
+        // A differing member past every chain block's 32 bytes (an empty record at the row's end: trailing tombstones
+        // or unknown members that B includes) shifts nothing the chain reads: s stays the shift of the bytes before it,
+        // which the clean blocks up to the last block and the last block's own run are placed by. Such members are the
+        // last differing ones of the row, so the shifts before the others do not contain theirs.
+        if (__ballot(dl && !vd)) (void)wscan_excl((uint32_t)(vd ? Lr - Lbm : 0), tot);
         // the last block of every run before this member: the open run's, or the previous valid member's (a prefix max)
         const int32_t px = dpp_scan_imax(vd ? khi : (-0x7FFFFFFF - 1));
         const int32_t pxe = (int32_t)dpp_shr1((uint32_t)px, 0x80000000u);   // (exclusive: the lanes below this one)

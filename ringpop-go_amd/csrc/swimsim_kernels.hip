@@ -216,7 +216,10 @@ __device__ __forceinline__ void fold_row(const DS &d, uint32_t ol, int dping, in
     }
     if (napp || evict) d.dirty[ol] = 1;                            // ComputeChecksum pending
     if (dlen) d.clen[ol] = clen0 + (uint32_t)dlen;
-    if (maxlast > clast0) d.clast[ol] = maxlast;
+    // (an invalidated clast stays invalidated until member N - 1 is included again: the kernels rescan it without
+    // storing what they find, and a member applied after the invalidation may lie below the row's true last
+    // included member)
+    if ((clast0 != -2 || maxlast == (int)d.N - 1) && maxlast > clast0) d.clast[ol] = maxlast;
     else if (inval) d.clast[ol] = -2;                              // rescanned by the checksum kernel
     if (nref) ctr_add(d, C_REFUTES, (unsigned long long)nref);
 }
@@ -285,7 +288,7 @@ __device__ __forceinline__ void fold_row_pre(const DS &d, uint32_t ol, RowPre &p
     }
     if (napp || evict) { p.dirty = 1; if (l0) d.dirty[ol] = 1; }  // ComputeChecksum pending
     if (dlen) { p.clen += (uint32_t)dlen; if (l0) d.clen[ol] = p.clen; }
-    if (maxlast > p.clast) { p.clast = maxlast; if (l0) d.clast[ol] = maxlast; }
+    if ((p.clast != -2 || maxlast == (int)d.N - 1) && maxlast > p.clast) { p.clast = maxlast; if (l0) d.clast[ol] = maxlast; }   // (as fold_row)
     else if (inval) { p.clast = -2; if (l0) d.clast[ol] = -2; }   // rescanned by the checksum kernel
     if (nref && l0) ctr_add(d, C_REFUTES, (unsigned long long)nref);
 }

@@ -200,7 +200,8 @@ def _events(events):
 
 def make_config(n, *, t0_ms=T0_MS, period_ms=200, suspect_ms=5000, faulty_ms=24 * 3600 * 1000, tombstone_ms=60_000,
                 ping_request_size=3, max_rfs_jobs=5, p_factor=15, seed=1, device=0, max_rounds=0,
-                message_pool_bytes=0, observer_range=None, tuning=None):
+                message_pool_bytes=0, observer_range=None, tuning=None, addresses=None):
+    """addresses: n fixed-width (13..20 bytes), strictly ascending member addresses (None: the synthetic 19-byte ones)"""
     cfg = Config()
     cfg.num_members, cfg.device, cfg.t0_ms, cfg.protocol_period_ms = n, device, t0_ms, period_ms
     cfg.suspect_timeout_ms, cfg.faulty_timeout_ms, cfg.tombstone_timeout_ms = suspect_ms, faulty_ms, tombstone_ms
@@ -211,7 +212,20 @@ def make_config(n, *, t0_ms=T0_MS, period_ms=200, suspect_ms=5000, faulty_ms=24 
     cfg._tuning = make_tuning(tuning)               # kept alive with the config
     if cfg._tuning is not None:
         cfg.tuning = C.cast(C.pointer(cfg._tuning), C.c_void_p)
+    cfg._addr_buf = None                            # kept alive with the config
+    if addresses is not None:
+        if len(addresses) != n:
+            raise ValueError(f"{len(addresses)} addresses for {n} members")
+        cfg._addr_buf, cfg.addr_stride = pack_addresses(addresses)
+        cfg.addresses = C.cast(cfg._addr_buf, C.c_char_p)
     return cfg
+
+
+def pack_addresses(addresses):
+    """(buffer, stride) of swimsim_config.addresses: the addresses back to back, each padded with NULs to the longest"""
+    stride = max(len(a) for a in addresses)
+    buf = b"".join(a.encode().ljust(stride, b"\0") for a in addresses)
+    return C.create_string_buffer(buf, len(buf)), stride
 
 
 def shard_range(n, nshards, rank):
@@ -266,11 +280,10 @@ class Cluster:
             cfg.tuning = C.cast(C.pointer(self._tuning), C.c_void_p)
         self._addr_buf = None
         if addresses is not None:
-            stride = max(len(a) for a in addresses)
-            buf = b"".join(a.encode().ljust(stride, b"\0") for a in addresses)
-            self._addr_buf = C.create_string_buffer(buf, len(buf))
+            if len(addresses) != n:
+                raise ValueError(f"{len(addresses)} addresses for {n} members")
+            self._addr_buf, cfg.addr_stride = pack_addresses(addresses)
             cfg.addresses = C.cast(self._addr_buf, C.c_char_p)
-            cfg.addr_stride = stride
         h = C.c_void_p()
         rc = L.swimsim_create(C.byref(cfg), C.byref(h))
         if rc != 0:
@@ -641,7 +654,8 @@ class ShardedCluster:
     def __init__(self, n, nshards, *, devices=None, init="converged", **kw):
         L = load_library()
         self.n, self.nshards = n, nshards
-        cfg = make_config(n, **{k: v for k, v in kw.items() if k != "addresses"})
+        cfg = make_config(n, **kw)                   # (addresses included: every shard hashes the same strings)
+        self._cfg = cfg                              # the address buffer and the tuning block live with the object
         arr = (C.c_void_p * nshards)()
         devs = (C.c_int32 * nshards)(*devices) if devices else None
         rc = L.swimsim_group_create(C.byref(cfg), nshards, C.cast(devs, C.c_void_p) if devs else None, arr)
