@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define SWIMSIM_ABI_VERSION 7
+#define SWIMSIM_ABI_VERSION 8
 
 enum {
     SWIMSIM_OK = 0,
@@ -283,6 +283,42 @@ typedef struct swimsim_memory_t {
     uint64_t lazy_fallbacks;
 } swimsim_memory_t;
 int swimsim_memory(swimsim_t *h, swimsim_memory_t *out);
+
+/* ---- member census (ABI 8): how the cluster sees each member ----
+ * No reference counterpart: these stand in for polling NodeInterface.MemberStats (stats.go:41-52) on every node and
+ * counting, per member, the states the nodes hold it in. A census is a read-only column reduction over the handle's
+ * observer rows on the device: it changes no state and no result of the round.
+ *
+ * swimsim_census: counts[i*6 + s] = the number of counted observer rows of this handle that hold member members[i] in
+ * status s: 0..4 = alive, suspect, faulty, leave, tombstone, 5 = unknown (the row word's SWIMSIM_UNKNOWN, evicted
+ * members included). min_inc_ms[i] / max_inc_ms[i] (either may be NULL) = the smallest / largest incarnation over the
+ * counted rows that know the member, both -1 when none does. who = SWIMSIM_CENSUS_LIVE counts the owned rows whose
+ * observer is live now (the table swimsim_set_live and the kill / revive events write), SWIMSIM_CENSUS_ALL every owned
+ * row; an observer's own cell counts like any other. members = NULL: every member in index order, and n must be N;
+ * else n indices below N (duplicates allowed), and the read-back is proportional to n. ms (may be NULL) receives the
+ * HIP-event time of the device work. One host synchronisation per call. SWIMSIM_EINVAL, before any device work: NULL
+ * handle or counts, n = 0, an index >= N, NULL members with n != N, an unknown who.
+ *
+ * swimsim_trace_members: track n <= 64 members (more, or an index >= N: SWIMSIM_EINVAL) in a buffer of rounds_cap
+ * (1..65,536) records allocated here (SWIMSIM_ENOMEM). While a trace is set every round of swimsim_step appends, with
+ * one kernel after phase C and no host round trip, the record {round, live owned observers, counts[n][6] over the live
+ * owned rows}; with rounds_cap records held, later rounds are dropped and counted. A new call replaces the set and
+ * clears the records; n = 0 switches the trace off and frees it.
+ *
+ * swimsim_trace_read: drains the trace in round order: at most cap records are written (rounds[k], nlive[k],
+ * counts[k*n*6 ...]; each may be NULL), *n = the records held, *dropped = the rounds lost since the last drain. The
+ * trace is empty afterwards and keeps recording. No trace set: *n = 0.
+ *
+ * Shards: a handle counts its own rows, and every shard keeps the whole live table (swimsim_set_live). Counts add
+ * across shards; incarnation minima and maxima combine across shards with -1 as the identity; nlive adds across shards,
+ * and the shards' records line up by round. Census scratch and the trace buffer are allocated on first use: a handle
+ * that never calls these keeps the swimsim_memory figures it had. */
+enum { SWIMSIM_CENSUS_LIVE = 0, SWIMSIM_CENSUS_ALL = 1 };
+int swimsim_census(swimsim_t *h, const uint32_t *members, size_t n, int32_t who, uint32_t *counts, int64_t *min_inc_ms,
+                   int64_t *max_inc_ms, double *ms);
+int swimsim_trace_members(swimsim_t *h, const uint32_t *members, size_t n, uint32_t rounds_cap);
+int swimsim_trace_read(swimsim_t *h, uint32_t *rounds, uint32_t *nlive, uint32_t *counts, size_t cap, size_t *n,
+                       uint32_t *dropped);
 
 /* ---- measurement ---- */
 /* average device time (ms) of each kernel family since the last reset, for roofline reporting */

@@ -6,6 +6,7 @@
 // CPU fallback: if the device is unusable, swimsim_create() fails.
 #include "swimsim_kernels.hip"
 #include "swimsim_xchg.hip"
+#include "swimsim_census.hip"
 
 #include <hipcub/hipcub.hpp>
 #include <rccl/rccl.h>
@@ -385,6 +386,18 @@ struct swimsim {
     std::vector<unsigned long long *> wevt_h;
     uint4 *wout = nullptr;
     uint32_t *winfo = nullptr;
+    // member census (swimsim_census, swimsim_census.hip), every buffer allocated at the first call that needs it: the
+    // partial slabs of k_census; the chunk partials, counted rows and ticket of k_census_cols; the listed columns and
+    // the result rows (cn_cap entries each)
+    uint32_t *cn_slab = nullptr, *cn_part = nullptr, *cn_nlp = nullptr, *cn_ticket = nullptr, *cn_cols = nullptr,
+             *cn_res = nullptr;
+    size_t cn_cap = 0;
+    hipEvent_t cn_ev[2] = {nullptr, nullptr};
+    // per-round trace of tr_n tracked members (swimsim_trace_members): tr_buf holds tr_cap records of 2 + 6 * tr_n words,
+    // tr_state = {write cursor, dropped rounds, ticket}; k_census_cols appends one record per round (step_one)
+    uint32_t *tr_cols = nullptr, *tr_buf = nullptr, *tr_part = nullptr, *tr_nlp = nullptr, *tr_state = nullptr;
+    uint32_t tr_n = 0, tr_cap = 0;
+    size_t tr_bytes[5] = {0, 0, 0, 0, 0};         // what the five trace buffers hold of alloc_bytes
     // reference-row checksum path (swimsim_checksum_ref.hip + swimsim_checksum_csr.hip), allocated at its first launch
     // (on for wide launches by default: the bench window runs 9.51 against 10.48 ms per round)
     int csr_mode = 1;                             // swimsim_tuning.cs_ref: 0 off, 1 wide launches, 2 every launch of
@@ -447,6 +460,17 @@ int dalloc(swimsim *h, T **p, size_t count, const char *what) {
     h->alloc_bytes += bytes;
     *p = (T *)q;
     return 0;
+}
+
+// give back a dalloc'ed buffer of `bytes` (as dalloc counted them)
+template <typename T>
+void dfree(swimsim *h, T **p, size_t bytes) {
+    if (!*p) return;
+    auto it = std::find(h->allocs.begin(), h->allocs.end(), (void *)*p);
+    if (it != h->allocs.end()) h->allocs.erase(it);
+    hipFree(*p);
+    h->alloc_bytes -= bytes;
+    *p = nullptr;
 }
 
 hipEvent_t take_event(swimsim *h) {
@@ -1348,6 +1372,12 @@ void clock_offset_range(swimsim *h) {
     }
 }
 
+// row chunks (= waves) of a k_census_cols launch, and partial slabs of k_census
+inline uint32_t census_cols_chunks(const swimsim *h) {
+    return std::max(1u, (h->NL + CENSUS_COLS_CHUNK_ROWS - 1) / CENSUS_COLS_CHUNK_ROWS);
+}
+inline uint32_t census_chunks(const swimsim *h) { return std::max(1u, (h->NL + CENSUS_CHUNK_ROWS - 1) / CENSUS_CHUNK_ROWS); }
+
 int flush_events(swimsim *h, std::vector<uint4> &evs) {
     if (evs.empty()) return 0;
     Scope sc(h, F_EVENTS);
@@ -1684,6 +1714,11 @@ int step_one(swimsim *h, const swimsim_event *ev, size_t nev) {
     }
     // ---- C: checksums of dirty rows (on the side stream when few rows remain after dedup) ----
     if (int rc = checksum_dirty(h, 0, true)) return rc;
+    // ---- trace: one census record of the tracked members over the live owned rows (no host round trip) ----
+    if (h->tr_n)
+        hipLaunchKernelGGL(k_census_cols, dim3(census_cols_chunks(h)), dim3(64), 0, h->s, h->d, h->tr_cols, h->tr_n, 0u,
+                           h->tr_part, h->tr_nlp, h->tr_state + 2, h->tr_buf, 6u, h->tr_state, h->tr_cap,
+                           2u + 6u * h->tr_n, r);
     h->round++;
     h->host_ctr[SWIMSIM_C_ROUNDS]++;
     HIPCHK(h, hipGetLastError());
@@ -2107,6 +2142,8 @@ int swimsim_destroy(swimsim_t *h) {
     if (h->side) hipStreamDestroy(h->side);
     if (h->side2) hipStreamDestroy(h->side2);
     if (h->ev_csr2) hipEventDestroy(h->ev_csr2);
+    for (hipEvent_t e : h->cn_ev)
+        if (e) hipEventDestroy(e);
     if (h->s) hipStreamDestroy(h->s);
     delete h;
     return SWIMSIM_OK;
@@ -2863,6 +2900,166 @@ int swimsim_memory(swimsim_t *h, swimsim_memory_t *out) {
     out->dense_cap = h->d.dense_cap;
     out->side_cap = h->snap_cap;
     out->lazy_fallbacks = h->lazy_fallbacks;
+    return SWIMSIM_OK;
+}
+
+// ---- member census (swimsim_census.hip) ----
+namespace {
+
+// the handle's device for the calls that allocate on first use (a shard of a multi-GPU group may not be on the
+// caller's current device)
+struct DeviceScope {
+    int prev = -1, dev;
+    explicit DeviceScope(int d) : dev(d) {
+        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+        if (prev != dev) hipSetDevice(dev);
+    }
+    ~DeviceScope() {
+        if (prev >= 0 && prev != dev) hipSetDevice(prev);
+    }
+};
+
+void trace_free(swimsim *h) {
+    dfree(h, &h->tr_cols, h->tr_bytes[0]);
+    dfree(h, &h->tr_buf, h->tr_bytes[1]);
+    dfree(h, &h->tr_part, h->tr_bytes[2]);
+    dfree(h, &h->tr_nlp, h->tr_bytes[3]);
+    dfree(h, &h->tr_state, h->tr_bytes[4]);
+    h->tr_n = h->tr_cap = 0;
+}
+
+// bytes dalloc counts for `count` elements of `size` bytes
+inline size_t dalloc_bytes(size_t count, size_t size) { return std::max<size_t>(count * size, 16); }
+
+}  // namespace
+
+int swimsim_census(swimsim_t *h, const uint32_t *members, size_t n, int32_t who, uint32_t *counts, int64_t *min_inc_ms,
+                   int64_t *max_inc_ms, double *ms) {
+    if (!h) return SWIMSIM_EINVAL;
+    if (!counts || n == 0) return h->fail(SWIMSIM_EINVAL, "census: no output buffer or an empty member list");
+    if (who != SWIMSIM_CENSUS_LIVE && who != SWIMSIM_CENSUS_ALL) return h->fail(SWIMSIM_EINVAL, "census: unknown who %d", who);
+    if (!members && n != h->N) return h->fail(SWIMSIM_EINVAL, "census: every member means n = %u, not %zu", h->N, n);
+    if (members)
+        for (size_t i = 0; i < n; i++)
+            if (members[i] >= h->N) return h->fail(SWIMSIM_EINVAL, "census: member %u out of range", members[i]);
+    if (n > 0xFFFFFFFFull / CENSUS_NFIELDS) return h->fail(SWIMSIM_EINVAL, "census: list of %zu members too long", n);
+    DeviceScope ds(h->device);
+    const uint32_t nn = (uint32_t)n, all = who == SWIMSIM_CENSUS_ALL;
+    const bool by_cols = members && (uint64_t)nn * CENSUS_LIST_WORDS <= h->NP;
+    const uint32_t nch = census_chunks(h), nch2 = census_cols_chunks(h);
+    // scratch, on first use
+    if (n > h->cn_cap) {
+        if (h->cn_cols) { HIPCHK(h, stream_sync(h)); }
+        dfree(h, &h->cn_cols, dalloc_bytes(h->cn_cap, 4));
+        dfree(h, &h->cn_res, dalloc_bytes(h->cn_cap * CENSUS_NFIELDS, 4));
+        h->cn_cap = 0;
+        int rc = 0;
+        if ((rc = dalloc(h, &h->cn_cols, n, "census member list")) ||
+            (rc = dalloc(h, &h->cn_res, n * CENSUS_NFIELDS, "census result"))) {
+            dfree(h, &h->cn_cols, dalloc_bytes(n, 4));
+            return rc;
+        }
+        h->cn_cap = n;
+    }
+    if (by_cols && !h->cn_part) {
+        int rc = 0;
+        if ((rc = dalloc(h, &h->cn_part, (size_t)nch2 * (h->NP / CENSUS_LIST_WORDS) * CENSUS_NFIELDS, "census list partials")) ||
+            (rc = dalloc(h, &h->cn_nlp, nch2, "census row counts")) || (rc = dalloc(h, &h->cn_ticket, 1, "census ticket"))) {
+            h->cn_part = nullptr;
+            return rc;
+        }
+        HIPCHK(h, hipMemsetAsync(h->cn_ticket, 0, 4, h->s));
+    }
+    if (!by_cols && !h->cn_slab)
+        if (int rc = dalloc(h, &h->cn_slab, (size_t)nch * CENSUS_NFIELDS * h->NP, "census slabs")) return rc;
+    for (hipEvent_t &e : h->cn_ev)
+        if (!e) HIPCHK(h, hipEventCreate(&e));
+    if (members) HIPCHK(h, hipMemcpyAsync(h->cn_cols, members, n * 4, hipMemcpyHostToDevice, h->s));
+    HIPCHK(h, hipEventRecord(h->cn_ev[0], h->s));
+    if (by_cols) {
+        hipLaunchKernelGGL(k_census_cols, dim3(nch2), dim3(64), 0, h->s, h->d, h->cn_cols, nn, all, h->cn_part, h->cn_nlp,
+                           h->cn_ticket, h->cn_res, CENSUS_NFIELDS, (uint32_t *)nullptr, 0u, 0u, 0u);
+    } else {
+        hipLaunchKernelGGL(k_census, dim3((h->NP + CENSUS_BLOCK_COLS - 1) / CENSUS_BLOCK_COLS, nch), dim3(256), 0, h->s, h->d,
+                           all, h->cn_slab);
+        hipLaunchKernelGGL(k_census_sum, dim3(blocks_for_threads(nn)), dim3(256), 0, h->s, h->cn_slab, nch, h->NP,
+                           members ? h->cn_cols : (const uint32_t *)nullptr, nn, h->cn_res);
+    }
+    HIPCHK(h, hipEventRecord(h->cn_ev[1], h->s));
+    std::vector<uint32_t> res(n * CENSUS_NFIELDS);
+    HIPCHK(h, hipMemcpyAsync(res.data(), h->cn_res, res.size() * 4, hipMemcpyDeviceToHost, h->s));
+    HIPCHK(h, stream_sync(h));                                     // the call's one host synchronisation
+    HIPCHK(h, hipGetLastError());
+    if (ms) {
+        float t = 0;
+        HIPCHK(h, hipEventElapsedTime(&t, h->cn_ev[0], h->cn_ev[1]));
+        *ms = t;
+    }
+    for (size_t i = 0; i < n; i++) {
+        const uint32_t *v = &res[i * CENSUS_NFIELDS];
+        for (int s = 0; s < 6; s++) counts[i * 6 + s] = v[s];
+        if (min_inc_ms) min_inc_ms[i] = v[6] == 0xFFFFFFFFu ? -1 : from_e(h, v[6]);
+        if (max_inc_ms) max_inc_ms[i] = v[7] == 0 ? -1 : from_e(h, v[7] - 1);
+    }
+    return SWIMSIM_OK;
+}
+
+int swimsim_trace_members(swimsim_t *h, const uint32_t *members, size_t n, uint32_t rounds_cap) {
+    if (!h) return SWIMSIM_EINVAL;
+    if (n > CENSUS_TRACE_MAX) return h->fail(SWIMSIM_EINVAL, "trace: at most %u tracked members, not %zu", CENSUS_TRACE_MAX, n);
+    if (n) {
+        if (!members) return h->fail(SWIMSIM_EINVAL, "trace: no member list");
+        for (size_t i = 0; i < n; i++)
+            if (members[i] >= h->N) return h->fail(SWIMSIM_EINVAL, "trace: member %u out of range", members[i]);
+        if (rounds_cap < 1 || rounds_cap > 65536)
+            return h->fail(SWIMSIM_EINVAL, "trace: rounds_cap %u not in 1..65536", rounds_cap);
+    }
+    DeviceScope ds(h->device);
+    if (h->tr_n) {
+        HIPCHK(h, stream_sync(h));
+        trace_free(h);
+    }
+    if (!n) return SWIMSIM_OK;
+    const uint32_t nn = (uint32_t)n, nch2 = census_cols_chunks(h);
+    const size_t cnt[5] = {n, (size_t)rounds_cap * (2 + 6 * n), (size_t)nch2 * n * CENSUS_NFIELDS, nch2, 4};
+    for (int i = 0; i < 5; i++) h->tr_bytes[i] = dalloc_bytes(cnt[i], 4);
+    int rc = 0;
+    if ((rc = dalloc(h, &h->tr_cols, cnt[0], "trace members")) || (rc = dalloc(h, &h->tr_buf, cnt[1], "trace records")) ||
+        (rc = dalloc(h, &h->tr_part, cnt[2], "trace partials")) || (rc = dalloc(h, &h->tr_nlp, cnt[3], "trace row counts")) ||
+        (rc = dalloc(h, &h->tr_state, cnt[4], "trace cursor"))) {
+        trace_free(h);                                             // (a buffer that was not allocated is skipped)
+        return rc;
+    }
+    HIPCHK(h, hipMemcpyAsync(h->tr_cols, members, n * 4, hipMemcpyHostToDevice, h->s));
+    HIPCHK(h, hipMemsetAsync(h->tr_state, 0, 16, h->s));
+    HIPCHK(h, stream_sync(h));
+    h->tr_n = nn;
+    h->tr_cap = rounds_cap;
+    return SWIMSIM_OK;
+}
+
+int swimsim_trace_read(swimsim_t *h, uint32_t *rounds, uint32_t *nlive, uint32_t *counts, size_t cap, size_t *n,
+                       uint32_t *dropped) {
+    if (!h) return SWIMSIM_EINVAL;
+    if (n) *n = 0;
+    if (dropped) *dropped = 0;
+    if (!h->tr_n) return SWIMSIM_OK;
+    uint32_t st[2] = {0, 0};
+    HIPCHK(h, hipMemcpyAsync(st, h->tr_state, 8, hipMemcpyDeviceToHost, h->s));
+    HIPCHK(h, stream_sync(h));
+    const size_t held = std::min(st[0], h->tr_cap), rw = 2 + 6 * (size_t)h->tr_n;
+    std::vector<uint32_t> rec(held * rw);
+    if (held) HIPCHK(h, hipMemcpyAsync(rec.data(), h->tr_buf, rec.size() * 4, hipMemcpyDeviceToHost, h->s));
+    HIPCHK(h, hipMemsetAsync(h->tr_state, 0, 8, h->s));              // empty, and recording goes on
+    HIPCHK(h, stream_sync(h));
+    for (size_t i = 0; i < held && i < cap; i++) {
+        const uint32_t *v = &rec[i * rw];
+        if (rounds) rounds[i] = v[0];
+        if (nlive) nlive[i] = v[1];
+        if (counts) memcpy(counts + i * 6 * h->tr_n, v + 2, 6 * (size_t)h->tr_n * 4);
+    }
+    if (n) *n = held;
+    if (dropped) *dropped = st[1];
     return SWIMSIM_OK;
 }
 

@@ -35,6 +35,9 @@ COUNTER_NAMES = [
     "rfs_omitted", "timers_fired", "msg_changes", "heal_attempts", "heal_failures",
 ]
 T0_MS = 1_500_000_000_000
+CENSUS_LIVE, CENSUS_ALL = 0, 1                   # swimsim_census `who`
+CENSUS_WHO = {"live": CENSUS_LIVE, "all": CENSUS_ALL}
+CENSUS_STATUSES = ("alive", "suspect", "faulty", "leave", "tombstone", "unknown")   # columns of a census count
 ERRORS = {-1: "EINVAL", -2: "ENOMEM", -3: "EHIP", -4: "ECAPACITY", -5: "ERANGE"}
 
 
@@ -182,6 +185,9 @@ def load_library(path: str = LIB_PATH):
                                              C.POINTER(u32), C.POINTER(u32), C.POINTER(i32)]),
         "swimsim_protocol_stats": (C.c_int, [P, C.POINTER(ProtocolStatsC)]),
         "swimsim_memory": (C.c_int, [P, C.POINTER(MemoryC)]),
+        "swimsim_census": (C.c_int, [P, P, sz, i32, P, P, P, C.POINTER(C.c_double)]),
+        "swimsim_trace_members": (C.c_int, [P, P, sz, u32]),
+        "swimsim_trace_read": (C.c_int, [P, P, P, P, sz, C.POINTER(sz), C.POINTER(u32)]),
     }
     for name, (res, args) in sigs.items():
         f = getattr(L, name)
@@ -226,6 +232,15 @@ def pack_addresses(addresses):
     stride = max(len(a) for a in addresses)
     buf = b"".join(a.encode().ljust(stride, b"\0") for a in addresses)
     return C.create_string_buffer(buf, len(buf)), stride
+
+
+def _member_list(members):
+    """a member index list as the contiguous uint32 array the C ABI reads (negative or huge indices are refused here:
+    they would wrap into the 32-bit index)"""
+    a = np.asarray(members, dtype=np.int64).reshape(-1)
+    if len(a) and (a.min() < 0 or a.max() > 0xFFFFFFFF):
+        raise SwimsimError("EINVAL: member index out of range")
+    return np.ascontiguousarray(a, dtype=np.uint32)
 
 
 def shard_range(n, nshards, rank):
@@ -505,6 +520,52 @@ class Cluster:
         st, inc = self.row(o)
         return int(st[m]), int(inc[m])
 
+    # ---- member census (swimsim_census / swimsim_trace_*): how this handle's observers hold each member ----
+    def census(self, members=None, who="live"):
+        """(counts[n, 6], min_inc[n], max_inc[n], ms): per queried member (None: every member in index order) the
+        number of this handle's observer rows that hold it alive, suspect, faulty, leave, tombstone and unknown, and
+        the smallest and largest incarnation over the rows that know it (-1: none does). who = "live" counts the rows
+        of live observers, "all" every row (or a raw swimsim_census who value). One device pass, one host
+        synchronisation; ms is the device time."""
+        w = CENSUS_WHO.get(who, who) if isinstance(who, str) else who
+        if isinstance(w, str):
+            raise ValueError(f"census: who is 'live' or 'all', not {who!r}")
+        if members is None:
+            idx, ptr, n = None, None, self.n
+        else:
+            idx = _member_list(members)
+            ptr, n = idx.ctypes.data, len(idx)
+        counts = np.zeros((n, 6), np.uint32)
+        mn = np.zeros(n, np.int64)
+        mx = np.zeros(n, np.int64)
+        ms = C.c_double()
+        self._chk(load_library().swimsim_census(self.h, ptr, n, int(w), counts.ctypes.data, mn.ctypes.data,
+                                                mx.ctypes.data, C.byref(ms)))
+        return counts, mn, mx, ms.value
+
+    def trace_members(self, members, rounds_cap=4096):
+        """track up to 64 members: every round of step() then records, on the device, their census over the live
+        observer rows (trace()). An empty list switches the trace off; a new list replaces the old one and clears the
+        recorded rounds. rounds_cap records are kept between two trace() calls; later rounds are dropped and counted."""
+        idx = _member_list(members)
+        self._chk(load_library().swimsim_trace_members(self.h, idx.ctypes.data if len(idx) else None, len(idx),
+                                                       int(rounds_cap)))
+        self._trace_n, self._trace_cap = len(idx), int(rounds_cap) if len(idx) else 0
+
+    def trace(self):
+        """drain the trace: (rounds[k], nlive[k], counts[k, n, 6], dropped) in round order, n = the tracked members in
+        the order given to trace_members, nlive = the live observers of this handle in that round, dropped = rounds lost
+        to a full buffer since the last drain"""
+        n, cap = getattr(self, "_trace_n", 0), getattr(self, "_trace_cap", 0)
+        rounds = np.zeros(cap, np.uint32)
+        nlive = np.zeros(cap, np.uint32)
+        counts = np.zeros((cap, n, 6), np.uint32)
+        k, dropped = C.c_size_t(), C.c_uint32()
+        self._chk(load_library().swimsim_trace_read(self.h, rounds.ctypes.data, nlive.ctypes.data, counts.ctypes.data,
+                                                    cap, C.byref(k), C.byref(dropped)))
+        k = min(k.value, cap)
+        return rounds[:k].copy(), nlive[:k].copy(), counts[:k].copy(), dropped.value
+
     def node_stats(self, o):
         p, mx, ch, mem = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32()
         self._chk(load_library().swimsim_node_stats(self.h, o, C.byref(p), C.byref(mx), C.byref(ch), C.byref(mem)))
@@ -749,6 +810,31 @@ class ShardedCluster:
 
     def row(self, o):
         return self.owner(o).row(o)
+
+    # member census over all shards (include/swimsim.h): counts and nlive add, incarnation minima and maxima combine
+    # with -1 as the identity, and the shards' trace records line up by round
+    def census(self, members=None, who="live"):
+        parts = [c.census(members, who) for c in self.shards]
+        counts = sum(p[0].astype(np.uint64) for p in parts).astype(np.uint32)
+        big = np.iinfo(np.int64).max
+        mn = np.min([np.where(p[1] < 0, big, p[1]) for p in parts], axis=0)
+        mn = np.where(mn == big, -1, mn)
+        mx = np.max([p[2] for p in parts], axis=0)
+        return counts, mn, mx, sum(p[3] for p in parts)      # (the shards' passes run one after another)
+
+    def trace_members(self, members, rounds_cap=4096):
+        for c in self.shards:
+            c.trace_members(members, rounds_cap)
+
+    def trace(self):
+        parts = [c.trace() for c in self.shards]
+        rounds = parts[0][0]
+        for p in parts[1:]:
+            if not np.array_equal(p[0], rounds):
+                raise SwimsimError("trace: the shards recorded different rounds")
+        nlive = sum(p[1].astype(np.uint64) for p in parts).astype(np.uint32)
+        counts = sum(p[2].astype(np.uint64) for p in parts).astype(np.uint32)
+        return rounds, nlive, counts, max(p[3] for p in parts)
 
     def changes(self, o):
         return self.owner(o).changes(o)

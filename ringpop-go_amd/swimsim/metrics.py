@@ -1,0 +1,49 @@
+"""Failure-detection metrics from a member trace (Cluster.trace / ShardedCluster.trace).
+
+Plain numpy on the trace arrays: no device, no library. The status columns of a census count are alive, suspect,
+faulty, leave, tombstone, unknown (swimsim.CENSUS_STATUSES).
+"""
+from __future__ import annotations
+
+from dataclasses import dataclass
+
+import numpy as np
+
+ALIVE, SUSPECT, FAULTY, LEAVE, TOMBSTONE, UNKNOWN = range(6)
+
+
+@dataclass
+class DetectionTimes:
+    """per tracked member, the recorded round (None: never in the trace) in which
+    first_suspect: some live observer first held it suspect or worse (suspect, faulty, leave, tombstone);
+    first_faulty:  some live observer first held it faulty or worse (faulty, leave, tombstone);
+    all_faulty:    every live observer first held it faulty or worse, or no longer knew it (unknown: evicted)."""
+    first_suspect: list
+    first_faulty: list
+    all_faulty: list
+
+
+def _first(rounds, hit) -> list:
+    """per column of hit[k, n], the round of the first true entry"""
+    out: list = []
+    for j in range(hit.shape[1]):
+        ks = np.nonzero(hit[:, j])[0]
+        out.append(int(rounds[ks[0]]) if len(ks) else None)
+    return out
+
+
+def detection_times(rounds, nlive, counts) -> DetectionTimes:
+    """rounds[k], nlive[k], counts[k, n, 6] as trace() returns them (live observer rows). Rounds are looked at in the
+    order recorded; a gap in `rounds` (records dropped by a full buffer) is simply not seen: the answer is the first
+    RECORDED round. A round with no live observer detects nothing."""
+    rounds = np.asarray(rounds).reshape(-1)
+    nlive = np.asarray(nlive, dtype=np.int64).reshape(-1)
+    counts = np.asarray(counts, dtype=np.int64)
+    if counts.ndim != 3 or counts.shape[2] != 6 or counts.shape[0] != len(rounds) or len(nlive) != len(rounds):
+        raise ValueError("detection_times: rounds[k], nlive[k] and counts[k, n, 6] expected")
+    suspect_up = counts[:, :, SUSPECT:TOMBSTONE + 1].sum(axis=2)
+    faulty_up = counts[:, :, FAULTY:TOMBSTONE + 1].sum(axis=2)
+    gone = faulty_up + counts[:, :, UNKNOWN]
+    some_live = (nlive > 0)[:, None]
+    return DetectionTimes(_first(rounds, suspect_up > 0), _first(rounds, faulty_up > 0),
+                          _first(rounds, (gone == nlive[:, None]) & some_live))
