@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define SWIMSIM_ABI_VERSION 8
+#define SWIMSIM_ABI_VERSION 9
 
 enum {
     SWIMSIM_OK = 0,
@@ -319,6 +319,57 @@ int swimsim_census(swimsim_t *h, const uint32_t *members, size_t n, int32_t who,
 int swimsim_trace_members(swimsim_t *h, const uint32_t *members, size_t n, uint32_t rounds_cap);
 int swimsim_trace_read(swimsim_t *h, uint32_t *rounds, uint32_t *nlive, uint32_t *counts, size_t cap, size_t *n,
                        uint32_t *dropped);
+
+/* ---- key routing through every node's own ring view (ABI 9) ----
+ * Every Ringpop node feeds its consistent-hash ring from its own memberlist: alive and suspect members are servers,
+ * every other status is not (Ringpop.handleChanges, ringpop.go:550-563), and Lookup (ringpop.go:582-606) asks that
+ * ring. These calls answer, on the device, where observer o sends key k, for every observer row of the handle, without
+ * a ring per node. They are read-only: no state and no result of the round changes.
+ *
+ * The view ring of observer o with R replica points is the ring one AddRemoveServers builds on an empty
+ * hashring.HashRing: it adds every member whose cell in row o is alive or suspect, in ascending member index, and
+ * removes nothing. Its points are Fingerprint32(address(m) ‖ decimal(i)), i = 0..R-1; at an equal hash the lowest
+ * present member index owns the point (first inserter keeps it, rbtree.go:122-126); owner(o, k) is the member index of
+ * the first point >= Fingerprint32(key k) in (hash, member) order, wrapping to the first point; an empty ring gives -1.
+ *
+ * Deviation: a real node's ring depends on its history at a shared hash, because removing one server deletes the
+ * point for both (hashring.go:182-188); the view ring is the fresh build. With the synthetic addresses, N = 256 and
+ * R = 100, members 185 and 215 share replica hash 581480965 and "key-226936" (hash 581472960) is owned by 185 with
+ * every member present, by 215 without 185, by 97 without both, and by 97 in a ring from which 185 was removed after
+ * the build: the last is what a long-running node answers, 215 what the view ring answers.
+ *
+ * Keys are packed as for swimring_lookup_batch: key k is bytes [off[k], off[k+1]) of keys. mode: 0 = automatic, 1 =
+ * the ring walk for every row, 2 = the direct path for every row whose servers fit its list of 512 (diagnostics: the
+ * results are identical in every mode). replica_points is 1..1000 (with addresses of 13..20 bytes every replica string
+ * is then 14..23 bytes, one FarmHash length path). ms (may be NULL) receives the HIP-event time of the device work
+ * (without the point table, which is built at the first use of a replica_points value and kept).
+ *
+ * swimsim_route: owners[j*nkeys + k] = owner(observers[j], k). Observers must be rows of this handle; the read-back
+ * is proportional to nobs * nkeys.
+ *
+ * swimsim_route_census: who = SWIMSIM_CENSUS_LIVE or SWIMSIM_CENSUS_ALL selects the counted rows as for swimsim_census;
+ * *counted = their number. For key k, entries [hist_off[k], hist_off[k+1]) list every distinct owner over the counted
+ * rows, ascending by owner (-1 first), each with the number of counted rows that answer it; zero counts are omitted
+ * and the counts of one key sum to *counted. *nhist = the total number of entries; at most cap are written to
+ * hist_owner / hist_count and the caller retries with larger buffers (no error); hist_off (nkeys + 1 entries) is always
+ * complete. The device appends only the (key, owner) pairs that differ from the owner under the first counted row,
+ * sorts them and counts the runs: the result does not depend on arrival order, and a cluster that agrees writes
+ * nothing. One host synchronisation per pass over the rows when the views agree, one more to read the runs when they
+ * do not; a pass whose pairs overflow the buffer is run again over fewer keys, never truncated.
+ *
+ * SWIMSIM_EINVAL, before any device work: NULL handle (-1, nothing written), keys, off or output; nkeys = 0;
+ * replica_points outside 1..1000; an observer out of range or not owned; nobs = 0; an unknown who or mode; N above
+ * 524,288 (the row's presence bitmap is then more than 64 KB of LDS). SWIMSIM_ENOMEM leaves the handle usable.
+ *
+ * Shards: a handle routes over its own rows; histograms add across shards per (key, owner). Memory: the point table
+ * (12 bytes per member and replica point) and at most 256 MiB of scratch beyond it and the keys are allocated on first
+ * use and freed at destroy: a handle that never calls these launches what it launched and keeps the swimsim_memory
+ * figures it had. */
+int swimsim_route(swimsim_t *h, const uint8_t *keys, const uint64_t *off, size_t nkeys, uint32_t replica_points,
+                  const uint32_t *observers, size_t nobs, int32_t mode, int32_t *owners, double *ms);
+int swimsim_route_census(swimsim_t *h, const uint8_t *keys, const uint64_t *off, size_t nkeys, uint32_t replica_points,
+                         int32_t who, int32_t mode, uint32_t *counted, uint64_t *hist_off, int32_t *hist_owner,
+                         uint32_t *hist_count, size_t cap, size_t *nhist, double *ms);
 
 /* ---- measurement ---- */
 /* average device time (ms) of each kernel family since the last reset, for roofline reporting */

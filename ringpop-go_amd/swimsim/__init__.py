@@ -188,6 +188,9 @@ def load_library(path: str = LIB_PATH):
         "swimsim_census": (C.c_int, [P, P, sz, i32, P, P, P, C.POINTER(C.c_double)]),
         "swimsim_trace_members": (C.c_int, [P, P, sz, u32]),
         "swimsim_trace_read": (C.c_int, [P, P, P, P, sz, C.POINTER(sz), C.POINTER(u32)]),
+        "swimsim_route": (C.c_int, [P, P, P, sz, u32, P, sz, i32, P, C.POINTER(C.c_double)]),
+        "swimsim_route_census": (C.c_int, [P, P, P, sz, u32, i32, i32, C.POINTER(u32), P, P, P, sz, C.POINTER(sz),
+                                           C.POINTER(C.c_double)]),
     }
     for name, (res, args) in sigs.items():
         f = getattr(L, name)
@@ -243,6 +246,42 @@ def _member_list(members):
     return np.ascontiguousarray(a, dtype=np.uint32)
 
 
+def _pack_keys(keys):
+    """(bytes, offsets uint64[K + 1]) of a key list as swimsim_route and swimring_lookup_batch read it: the keys (str or
+    bytes) back to back, key k being bytes [off[k], off[k + 1])"""
+    bs = [k.encode() if isinstance(k, str) else bytes(k) for k in keys]
+    off = np.zeros(len(bs) + 1, np.uint64)
+    if bs:
+        off[1:] = np.cumsum([len(b) for b in bs])
+    return b"".join(bs), off
+
+
+def _census_who(who, what):
+    w = CENSUS_WHO.get(who, who) if isinstance(who, str) else who
+    if isinstance(w, str):
+        raise ValueError(f"{what}: who is 'live' or 'all', not {who!r}")
+    return int(w)
+
+
+def merge_route_histograms(parts):
+    """add per-shard route_census results (counted, hist_off, hist_owner, hist_count, ms) per (key, owner): the
+    histogram of the union of the shards' rows, in the same layout (owners ascending per key, -1 first)"""
+    K = len(parts[0][1]) - 1
+    counted = sum(int(p[0]) for p in parts)
+    key = np.concatenate([np.repeat(np.arange(K, dtype=np.int64), np.diff(p[1]).astype(np.int64)) for p in parts])
+    own = np.concatenate([np.asarray(p[2], np.int64) for p in parts])
+    cnt = np.concatenate([np.asarray(p[3], np.uint64) for p in parts])
+    pair = (key << 32) | (own + 1)                                   # ascending by key, then owner with -1 first
+    u, inv = np.unique(pair, return_inverse=True)
+    tot = np.zeros(len(u), np.uint64)
+    np.add.at(tot, inv, cnt)
+    keep = tot > 0
+    u, tot = u[keep], tot[keep]
+    off = np.zeros(K + 1, np.uint64)
+    off[1:] = np.cumsum(np.bincount(u >> 32, minlength=K))
+    return counted, off, ((u & 0xFFFFFFFF) - 1).astype(np.int32), tot.astype(np.uint32), sum(p[4] for p in parts)
+
+
 def shard_range(n, nshards, rank):
     """Observer rows of shard `rank` of `nshards` (the canonical split of include/swimsim.h)."""
     return n * rank // nshards, n * (rank + 1) // nshards
@@ -266,6 +305,7 @@ class Cluster:
         self.h, self.n, self.lo, self.nl = h, n, lo, nl
         self.t0_ms, self.period_ms = t0_ms, period_ms
         self._addr_buf = None
+        self._addresses = None
         self._listeners = {}
         return self
 
@@ -294,6 +334,7 @@ class Cluster:
         if self._tuning is not None:
             cfg.tuning = C.cast(C.pointer(self._tuning), C.c_void_p)
         self._addr_buf = None
+        self._addresses = list(addresses) if addresses is not None else None
         if addresses is not None:
             if len(addresses) != n:
                 raise ValueError(f"{len(addresses)} addresses for {n} members")
@@ -566,6 +607,46 @@ class Cluster:
         k = min(k.value, cap)
         return rounds[:k].copy(), nlive[:k].copy(), counts[:k].copy(), dropped.value
 
+    # ---- key routing through the observers' own ring views (swimsim_route / swimsim_route_census) ----
+    def route(self, keys, observers, replica_points=100, mode=0):
+        """int32 [nobs, K]: the member index observer observers[j] sends key k to, by the ring of the members its row
+        holds alive or suspect (-1: it holds none). keys are str or bytes; the observers must be rows of this handle.
+        mode 0 = automatic, 1 = ring walk, 2 = direct path (identical results)."""
+        blob, off = _pack_keys(keys)
+        obs = _member_list(observers)
+        out = np.empty((len(obs), len(off) - 1), np.int32)
+        ms = C.c_double()
+        self._chk(load_library().swimsim_route(self.h, blob, off.ctypes.data, len(off) - 1, int(replica_points),
+                                               obs.ctypes.data if len(obs) else None, len(obs), int(mode),
+                                               out.ctypes.data, C.byref(ms)))
+        self.last_route_ms = ms.value
+        return out
+
+    def route_census(self, keys, who="live", replica_points=100, mode=0):
+        """(counted, hist_off[K + 1], hist_owner, hist_count, ms): for key k, hist_owner / hist_count
+        [hist_off[k]:hist_off[k + 1]] are the distinct owners over the counted observer rows of this handle (ascending,
+        -1 first) and the number of rows that answer each; the counts of a key sum to counted. who as for census()."""
+        w = _census_who(who, "route_census")
+        blob, off = _pack_keys(keys)
+        K = len(off) - 1
+        cap = max(1, 2 * K)
+        while True:
+            hoff = np.zeros(K + 1, np.uint64)
+            own = np.empty(cap, np.int32)
+            cnt = np.empty(cap, np.uint32)
+            counted, nh, ms = C.c_uint32(), C.c_size_t(), C.c_double()
+            self._chk(load_library().swimsim_route_census(self.h, blob, off.ctypes.data, K, int(replica_points), w,
+                                                          int(mode), C.byref(counted), hoff.ctypes.data, own.ctypes.data,
+                                                          cnt.ctypes.data, cap, C.byref(nh), C.byref(ms)))
+            if nh.value <= cap:
+                return counted.value, hoff, own[:nh.value].copy(), cnt[:nh.value].copy(), ms.value
+            cap = nh.value
+
+    def address(self, m):
+        """member m's address (the synthetic one unless the cluster was given addresses)"""
+        a = getattr(self, "_addresses", None)
+        return a[m] if a is not None else address_of(m)
+
     def node_stats(self, o):
         p, mx, ch, mem = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32()
         self._chk(load_library().swimsim_node_stats(self.h, o, C.byref(p), C.byref(mx), C.byref(ch), C.byref(mem)))
@@ -729,6 +810,9 @@ class ShardedCluster:
             lo, hi = shard_range(n, nshards, i)
             self.shards.append(Cluster._adopt(C.c_void_p(arr[i]), n, lo, hi - lo, kw.get("t0_ms", T0_MS),
                                               kw.get("period_ms", 200)))
+        if kw.get("addresses") is not None:
+            for c in self.shards:
+                c._addresses = list(kw["addresses"])
         for c in self.shards:
             if init == "converged":
                 c._chk(L.swimsim_init_converged(c.h))
@@ -835,6 +919,26 @@ class ShardedCluster:
         nlive = sum(p[1].astype(np.uint64) for p in parts).astype(np.uint32)
         counts = sum(p[2].astype(np.uint64) for p in parts).astype(np.uint32)
         return rounds, nlive, counts, max(p[3] for p in parts)
+
+    # key routing over all shards: route goes to the shards that own the observers, histograms add per (key, owner)
+    def route(self, keys, observers, replica_points=100, mode=0):
+        obs = _member_list(observers)
+        if len(obs) and obs.max() >= self.n:
+            raise SwimsimError("EINVAL: route: observer out of range")
+        out = np.empty((len(obs), len(keys)), np.int32)
+        if not len(obs):
+            raise SwimsimError("EINVAL: route: no observers")
+        for c in self.shards:
+            sel = np.nonzero((obs >= c.lo) & (obs < c.lo + c.nl))[0]
+            if len(sel):
+                out[sel] = c.route(keys, obs[sel], replica_points, mode)
+        return out
+
+    def route_census(self, keys, who="live", replica_points=100, mode=0):
+        return merge_route_histograms([c.route_census(keys, who, replica_points, mode) for c in self.shards])
+
+    def address(self, m):
+        return self.shards[0].address(m)
 
     def changes(self, o):
         return self.owner(o).changes(o)
@@ -1030,3 +1134,8 @@ class Node:
 
     def ProtocolStats(self):                              # stats.go:81-104
         return self.c.protocol_stats()
+
+    def Lookup(self, key, replica_points=100):            # ringpop.go:582-606 over this node's own ring view
+        """(address, ok): the member this node sends `key` to; ok is False when its ring is empty"""
+        m = int(self.c.route([key], [self.o], replica_points)[0, 0])
+        return (self.c.address(m), True) if m >= 0 else ("", False)

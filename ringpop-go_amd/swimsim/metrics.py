@@ -1,4 +1,5 @@
-"""Failure-detection metrics from a member trace (Cluster.trace / ShardedCluster.trace).
+"""Failure-detection metrics from a member trace (Cluster.trace / ShardedCluster.trace) and routing agreement from
+a route census (Cluster.route_census / ShardedCluster.route_census).
 
 Plain numpy on the trace arrays: no device, no library. The status columns of a census count are alive, suspect,
 faulty, leave, tombstone, unknown (swimsim.CENSUS_STATUSES).
@@ -47,3 +48,37 @@ def detection_times(rounds, nlive, counts) -> DetectionTimes:
     some_live = (nlive > 0)[:, None]
     return DetectionTimes(_first(rounds, suspect_up > 0), _first(rounds, faulty_up > 0),
                           _first(rounds, (gone == nlive[:, None]) & some_live))
+
+
+@dataclass
+class RouteAgreement:
+    """per key of a route census:
+    distinct:  the number of distinct owners the counted rows answer (0: no row counted);
+    owner:     the plurality owner, the lowest owner among equals (-1 is an owner: the empty ring; -2: no row counted);
+    count:     the number of counted rows that answer the plurality owner."""
+    distinct: np.ndarray
+    owner: np.ndarray
+    count: np.ndarray
+
+    def agreed(self, counted) -> np.ndarray:
+        """per key: every counted row answers the same owner"""
+        return self.count == counted
+
+
+def route_agreement(counted, hist_off, hist_owner, hist_count) -> RouteAgreement:
+    """counted, hist_off[K + 1], hist_owner, hist_count as route_census() returns them (owners ascending per key)."""
+    hist_off = np.asarray(hist_off, dtype=np.int64).reshape(-1)
+    hist_owner = np.asarray(hist_owner, dtype=np.int64).reshape(-1)
+    hist_count = np.asarray(hist_count, dtype=np.int64).reshape(-1)
+    if len(hist_off) < 1 or len(hist_owner) != len(hist_count) or (len(hist_off) and hist_off[-1] != len(hist_owner)):
+        raise ValueError("route_agreement: hist_off[K + 1] and hist_owner / hist_count of hist_off[K] entries expected")
+    K = len(hist_off) - 1
+    distinct = np.diff(hist_off)
+    owner = np.full(K, -2, np.int64)
+    count = np.zeros(K, np.int64)
+    for k in range(K):
+        a, b = hist_off[k], hist_off[k + 1]
+        if b > a:
+            j = a + int(np.argmax(hist_count[a:b]))                  # (argmax takes the first: the lowest owner)
+            owner[k], count[k] = hist_owner[j], hist_count[j]
+    return RouteAgreement(distinct, owner, count)
