@@ -13,7 +13,8 @@
  *  - Status codes equal statePrecedence (member.go:112-128): alive 0, suspect 1, faulty 2,
  *    leave 3, tombstone 4. SWIMSIM_UNKNOWN (7) means "not in this node's memberlist".
  *  - Return values: 0 = OK, negative = SWIMSIM_E*. swimsim_last_error() gives the message.
- *    HIP errors are mapped, never aborted on.
+ *    HIP errors are mapped, never aborted on. A failed swimsim_create / swimsim_group_create
+ *    leaves no handle: swimsim_last_error(NULL) gives its message, on the thread that called it.
  *  - Calls on one handle must be serialized. swimsim_step() blocks and is deterministic.
  *  - The caller owns every output buffer (caller allocates, library fills). No device pointer
  *    escapes.
@@ -52,9 +53,11 @@ typedef struct swimsim_config {
     uint32_t suspect_timeout_ms;       /* StateTimeouts.Suspect, default 5 s (node.go:75) */
     uint32_t faulty_timeout_ms;        /* StateTimeouts.Faulty, default 24 h (node.go:76) */
     uint32_t tombstone_timeout_ms;     /* StateTimeouts.Tombstone, default 1 min (node.go:77) */
-    uint32_t ping_request_size;        /* PingRequestSize, default 3 (node.go:86) */
+    uint32_t ping_request_size;        /* PingRequestSize, default 3 (node.go:86). At most 8; more: SWIMSIM_EINVAL */
     uint32_t max_reverse_full_sync_jobs; /* MaxReverseFullSyncJobs, default 5 (node.go:96) */
-    uint32_t p_factor;                 /* disseminator pFactor, default 15 (disseminator.go:35) */
+    uint32_t p_factor;                 /* disseminator pFactor, default 15 (disseminator.go:35). The piggyback
+                                          counter has 8 bits: p_factor * digits10(max(N - 1, 1)), the largest
+                                          maxP of the handle, must be at most 255, else SWIMSIM_EINVAL */
     uint64_t seed;                     /* Philox key (docs/ROUND_SEMANTICS.md §6) */
     const char *addresses;             /* NULL: synthetic "10.%03u.%03u.%03u:7000"; else N fixed-width,
                                           strictly ascending addresses, each addr_stride bytes (shorter ones

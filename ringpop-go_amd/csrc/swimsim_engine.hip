@@ -1834,17 +1834,24 @@ extern "C" {
 
 int swimsim_abi_version(void) { return SWIMSIM_ABI_VERSION; }
 
-const char *swimsim_last_error(swimsim_t *h) { return h ? h->err.c_str() : "null handle"; }
+// a failed swimsim_create leaves no handle: its message stays with the calling thread, for swimsim_last_error(NULL)
+static thread_local std::string create_err;
+
+const char *swimsim_last_error(swimsim_t *h) {
+    if (h) return h->err.c_str();
+    return create_err.empty() ? "null handle" : create_err.c_str();
+}
 
 int swimsim_create(const swimsim_config *cfg, swimsim_t **out) {
     if (!cfg || !out) return SWIMSIM_EINVAL;
     *out = nullptr;
     swimsim *h = new swimsim();
+    create_err.clear();
     auto bail = [&](int rc) {
+        create_err = h->err;
         swimsim_destroy(h);
         return rc;
     };
-    static thread_local std::string create_err;
     h->N = cfg->num_members;
     if (h->N < 1 || h->N >= (1u << 24)) return bail(SWIMSIM_EINVAL);
     h->NP = (h->N + 63) & ~63u;
@@ -1865,9 +1872,23 @@ int swimsim_create(const swimsim_config *cfg, swimsim_t **out) {
     h->to_faulty = tf / h->period;
     h->to_tomb = tt / h->period;
     h->K = cfg->ping_request_size ? cfg->ping_request_size : 3;
-    if (h->K > 8) return bail(SWIMSIM_EINVAL);
+    if (h->K > 8) {                                   // (k_helpers keeps a node's helpers in registers)
+        h->err = "ping_request_size " + std::to_string(h->K) + " is above the limit of 8";
+        return bail(SWIMSIM_EINVAL);
+    }
     h->maxjobs = cfg->max_reverse_full_sync_jobs ? cfg->max_reverse_full_sync_jobs : 5;
     h->pfactor = cfg->p_factor ? cfg->p_factor : 15;
+    {
+        // a dissemination cell keeps the piggyback count p in 8 bits and 0xFF means "no entry" (swimsim_device.h): an
+        // entry leaves at p + 1 >= maxP, so p stays below 0xFF as long as maxP <= 255. The largest maxP this handle
+        // can compute is pFactor * digits10(N - 1), every other member pingable
+        const uint64_t maxp = (uint64_t)h->pfactor * (uint64_t)digits10((int32_t)std::max<uint32_t>(h->N - 1, 1u));
+        if (maxp > 255) {
+            h->err = "p_factor " + std::to_string(h->pfactor) + " gives maxP " + std::to_string(maxp) + " at " +
+                     std::to_string(h->N) + " members: the 8-bit piggyback counter holds maxP up to 255";
+            return bail(SWIMSIM_EINVAL);
+        }
+    }
     h->seed = cfg->seed;
     h->device = (int)cfg->device;
     // addresses

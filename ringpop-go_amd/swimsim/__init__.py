@@ -230,6 +230,12 @@ def make_config(n, *, t0_ms=T0_MS, period_ms=200, suspect_ms=5000, faulty_ms=24 
     return cfg
 
 
+def _create_message():
+    """": <text>" of this thread's last failed swimsim_create / swimsim_group_create ("" where it left none)"""
+    msg = load_library().swimsim_last_error(None).decode()
+    return f": {msg}" if msg and msg != "null handle" else ""
+
+
 def pack_addresses(addresses):
     """(buffer, stride) of swimsim_config.addresses: the addresses back to back, each padded with NULs to the longest"""
     stride = max(len(a) for a in addresses)
@@ -343,7 +349,7 @@ class Cluster:
         h = C.c_void_p()
         rc = L.swimsim_create(C.byref(cfg), C.byref(h))
         if rc != 0:
-            raise SwimsimError(f"swimsim_create failed: {ERRORS.get(rc, rc)}")
+            raise SwimsimError(f"swimsim_create failed: {ERRORS.get(rc, rc)}{_create_message()}")
         self.h = h
         self.lo = observer_range[0] if observer_range else 0
         self.nl = (observer_range[1] - observer_range[0]) if observer_range else n
@@ -802,7 +808,7 @@ class ShardedCluster:
         devs = (C.c_int32 * nshards)(*devices) if devices else None
         rc = L.swimsim_group_create(C.byref(cfg), nshards, C.cast(devs, C.c_void_p) if devs else None, arr)
         if rc != 0:
-            raise SwimsimError(f"swimsim_group_create failed: {ERRORS.get(rc, rc)}")
+            raise SwimsimError(f"swimsim_group_create failed: {ERRORS.get(rc, rc)}{_create_message()}")
         self._arr = arr
         self.live = np.ones(n, bool)
         self.shards = []
