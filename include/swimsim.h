@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define SWIMSIM_ABI_VERSION 9
+#define SWIMSIM_ABI_VERSION 10
 
 enum {
     SWIMSIM_OK = 0,
@@ -373,6 +373,51 @@ int swimsim_route(swimsim_t *h, const uint8_t *keys, const uint64_t *off, size_t
 int swimsim_route_census(swimsim_t *h, const uint8_t *keys, const uint64_t *off, size_t nkeys, uint32_t replica_points,
                          int32_t who, int32_t mode, uint32_t *counted, uint64_t *hist_off, int32_t *hist_owner,
                          uint32_t *hist_count, size_t cap, size_t *nhist, double *ms);
+
+/* ---- replica sets through every node's own ring view (ABI 10) ----
+ * Ringpop's second routing call, LookupN (ringpop.go:611, hashring.go:268-301), returns the n distinct servers that
+ * hold a key; replica.Replicator fans reads and writes out over that set (replica/replicator.go:170-213, NValue 3).
+ * These calls answer it through the view ring of every observer row (the ring of ABI 9 above: the fresh
+ * AddRemoveServers build from the members row o holds alive or suspect; its deviation note applies unchanged). They are
+ * read-only as the ABI 9 calls are. cnt(o) is the view's server count.
+ *
+ * prefs(o, k, n), 1 <= n <= 16:
+ *   cnt(o) <= n   every server of the view in ascending member index, cnt(o) entries (hashring.go:280-282, the rule of
+ *                 swimring_lookup_n_batch); an empty view gives 0 entries.
+ *   otherwise     start at the first REAL point >= Fingerprint32(k) in (hash, member) order, wrap once, and list each
+ *                 distinct owner at its first occurrence until n are listed.
+ * A point is real only for the lowest present member at its hash: when present members a < b share a replica hash the
+ * tree holds one node, a's (rbtree.go:122-126), and b's replica is not a point of this view: it must not add b to the
+ * list. If a is absent, b's point is real. Lookup never sees this (a comes first in the walk); LookupN does: with the
+ * synthetic addresses, N = 256, R = 100 and every member present, members 185 and 215 share replica hash 581480965 and
+ * prefs(o, "key-226936", 3) = 185, 97, 55, not 185, 215, 97. The order is the walk's order, a stronger promise than the
+ * reference's (which returns from a Go map) and the one swimring_lookup_n_batch makes.
+ *
+ * swimsim_route_n: prefs[(j*nkeys + k)*n + i], i < min(n, cnt(observers[j])), is the list; the rest of the n slots is
+ * -1. servers[j] (may be NULL) = cnt(observers[j]). keys, off, replica_points, mode, ms and the rule that observers are
+ * rows of this handle are those of swimsim_route; mode 2 takes the direct path for rows of n < cnt <= 512 servers.
+ *
+ * swimsim_replica_census: who, *counted, cap / *nhist (retry with larger buffers, no error) and the always-complete
+ * hist_off are those of swimsim_route_census. For key k, entries [hist_off[k], hist_off[k+1]) list every member that is
+ * in the replica set of k under at least one counted row, ascending by member, each with the number of counted rows
+ * whose set holds it (the sets are unordered here). Zero counts are omitted, every count is <= *counted, and the counts
+ * of one key sum to the sum over the counted rows of min(n, cnt(row)). All counted rows agree on key k's replica set
+ * exactly when every listed member has count = *counted. The device appends, per row and key, only the members by
+ * which the row's set differs from the set under the first counted row (a cluster that agrees writes nothing), sorts
+ * them and counts the runs, as swimsim_route_census does; a pass that overflows the buffer is run again over fewer keys.
+ *
+ * SWIMSIM_EINVAL, before any device work and with nothing written: every case of the ABI 9 calls, and n = 0 or
+ * n > 16. SWIMSIM_ENOMEM leaves the handle usable. Shards: as for ABI 9; histograms add per (key, member). Memory: on
+ * first use, freed at destroy; beside the ABI 9 buffers (which these calls share, the point table included) nkeys * n
+ * words for the base sets, and the census's pair buffers hold at least 2 * n * (rows of the handle) pairs of 28 bytes
+ * (448 MiB for 524,288 rows and n = 16). A handle that never calls these launches what it launched and keeps the
+ * swimsim_memory figures it had; swimsim_route and swimsim_route_census keep their kernels and results. */
+int swimsim_route_n(swimsim_t *h, const uint8_t *keys, const uint64_t *off, size_t nkeys, uint32_t replica_points,
+                    uint32_t n, const uint32_t *observers, size_t nobs, int32_t mode, int32_t *prefs, uint32_t *servers,
+                    double *ms);
+int swimsim_replica_census(swimsim_t *h, const uint8_t *keys, const uint64_t *off, size_t nkeys, uint32_t replica_points,
+                           uint32_t n, int32_t who, int32_t mode, uint32_t *counted, uint64_t *hist_off,
+                           int32_t *hist_member, uint32_t *hist_count, size_t cap, size_t *nhist, double *ms);
 
 /* ---- measurement ---- */
 /* average device time (ms) of each kernel family since the last reset, for roofline reporting */

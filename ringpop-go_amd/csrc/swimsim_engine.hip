@@ -413,6 +413,10 @@ struct swimsim {
     uint64_t *rt_off = nullptr;
     uint32_t *rt_kh = nullptr, *rt_p0 = nullptr, *rt_rows = nullptr, *rt_cnt = nullptr;
     int32_t *rt_base = nullptr, *rt_own = nullptr;
+    // replica sets (swimsim_route_n / swimsim_replica_census): the routed rows' server counts and the base sets [K][n]
+    uint32_t *rt_srv = nullptr;
+    int32_t *rt_nbase = nullptr;
+    size_t rt_srv_cap = 0, rt_nbase_cap = 0;
     unsigned long long *rt_exc = nullptr, *rt_exc2 = nullptr, *rt_uniq = nullptr, *rt_cur = nullptr;
     void *rt_cub = nullptr;
     size_t rt_bytes_cap = 0, rt_keys_cap = 0, rt_rows_cap = 0, rt_own_cap = 0, rt_exc_cap = 0, rt_cub_bytes = 0;
@@ -3228,6 +3232,51 @@ int route_keys(swimsim *h, const uint8_t *keys, const uint64_t *off, size_t nkey
     return 0;
 }
 
+// the census scratch, allocated at the first census of the handle: E exception pairs (appended, sorted, run-length encoded
+// with counts), the cursor and the hipcub scratch. E is at least `floor`, the most pairs a pass over one key can append
+// (NL for swimsim_route_census, 2n * NL for swimsim_replica_census), so that halving the keys of an overflowing pass
+// ends; a buffer that is below a later call's floor is replaced.
+int route_exc_scratch(swimsim *h, size_t floor) {
+    if (h->rt_exc && h->rt_exc_cap >= floor) return 0;
+    if (h->rt_exc) {
+        HIPCHK(h, stream_sync(h));
+        uint8_t *cub8 = static_cast<uint8_t *>(h->rt_cub);
+        dfree(h, &h->rt_exc, dalloc_bytes(h->rt_exc_cap, 8));
+        dfree(h, &h->rt_exc2, dalloc_bytes(h->rt_exc_cap, 8));
+        dfree(h, &h->rt_uniq, dalloc_bytes(h->rt_exc_cap, 8));
+        dfree(h, &h->rt_cnt, dalloc_bytes(h->rt_exc_cap, 4));
+        dfree(h, &h->rt_cur, dalloc_bytes(2, 8));
+        dfree(h, &cub8, dalloc_bytes(h->rt_cub_bytes, 1));
+        h->rt_cub = nullptr;
+        h->rt_cub_bytes = h->rt_exc_cap = 0;
+    }
+    size_t E = std::min(ROUTE_EXC_MAX, std::max(ROUTE_EXC_MIN, (size_t)h->NL * 64));
+    if (const char *v = getenv("SWIMSIM_ROUTE_EXC_CAP")) E = (size_t)strtoull(v, nullptr, 10);   // (tests: the chunked passes)
+    E = std::min<size_t>(std::max<size_t>(E, floor), (size_t)1 << 30);
+    size_t b1 = 0, b2 = 0;
+    hipcub::DoubleBuffer<unsigned long long> probe(nullptr, nullptr);
+    HIPCHK(h, hipcub::DeviceRadixSort::SortKeys(nullptr, b1, probe, (int)E, 0, 64, h->s));
+    HIPCHK(h, hipcub::DeviceRunLengthEncode::Encode(nullptr, b2, (unsigned long long *)nullptr, (unsigned long long *)nullptr,
+                                                   (uint32_t *)nullptr, (uint32_t *)nullptr, (int)E, h->s));
+    const size_t cb = std::max(b1, b2);
+    uint8_t *cub8 = nullptr;
+    int rc = 0;
+    if ((rc = dalloc(h, &h->rt_exc, E, "route exception pairs")) || (rc = dalloc(h, &h->rt_exc2, E, "route sorted pairs")) ||
+        (rc = dalloc(h, &h->rt_uniq, E, "route runs")) || (rc = dalloc(h, &h->rt_cnt, E, "route run counts")) ||
+        (rc = dalloc(h, &h->rt_cur, 2, "route cursor")) || (rc = dalloc(h, &cub8, cb, "route sort scratch"))) {
+        dfree(h, &h->rt_exc, dalloc_bytes(E, 8));
+        dfree(h, &h->rt_exc2, dalloc_bytes(E, 8));
+        dfree(h, &h->rt_uniq, dalloc_bytes(E, 8));
+        dfree(h, &h->rt_cnt, dalloc_bytes(E, 4));
+        dfree(h, &h->rt_cur, dalloc_bytes(2, 8));
+        return rc;
+    }
+    h->rt_cub = cub8;
+    h->rt_cub_bytes = cb;
+    h->rt_exc_cap = E;
+    return 0;
+}
+
 RouteArgs route_args(swimsim *h, const swimsim::RouteTable *tab, size_t nkeys, int32_t mode) {
     RouteArgs a{};
     a.pts = tab->pts; a.hm = tab->hm; a.P = h->N * tab->R; a.R = tab->R;
@@ -3304,32 +3353,7 @@ int swimsim_route_census(swimsim_t *h, const uint8_t *keys, const uint64_t *off,
     }
     // scratch, on first use: the exception pairs of one pass. A pass over one key appends at most NL pairs, so a
     // buffer of at least NL pairs always ends the chunking below
-    if (!h->rt_exc) {
-        size_t E = std::min(ROUTE_EXC_MAX, std::max(ROUTE_EXC_MIN, (size_t)h->NL * 64));
-        if (const char *v = getenv("SWIMSIM_ROUTE_EXC_CAP")) E = (size_t)strtoull(v, nullptr, 10);   // (tests: the chunked passes)
-        E = std::min<size_t>(std::max<size_t>(E, h->NL), (size_t)1 << 30);
-        size_t b1 = 0, b2 = 0;
-        hipcub::DoubleBuffer<unsigned long long> probe(nullptr, nullptr);
-        HIPCHK(h, hipcub::DeviceRadixSort::SortKeys(nullptr, b1, probe, (int)E, 0, 64, h->s));
-        HIPCHK(h, hipcub::DeviceRunLengthEncode::Encode(nullptr, b2, (unsigned long long *)nullptr, (unsigned long long *)nullptr,
-                                                       (uint32_t *)nullptr, (uint32_t *)nullptr, (int)E, h->s));
-        const size_t cb = std::max(b1, b2);
-        uint8_t *cub8 = nullptr;
-        int rc = 0;
-        if ((rc = dalloc(h, &h->rt_exc, E, "route exception pairs")) || (rc = dalloc(h, &h->rt_exc2, E, "route sorted pairs")) ||
-            (rc = dalloc(h, &h->rt_uniq, E, "route runs")) || (rc = dalloc(h, &h->rt_cnt, E, "route run counts")) ||
-            (rc = dalloc(h, &h->rt_cur, 2, "route cursor")) || (rc = dalloc(h, &cub8, cb, "route sort scratch"))) {
-            dfree(h, &h->rt_exc, dalloc_bytes(E, 8));
-            dfree(h, &h->rt_exc2, dalloc_bytes(E, 8));
-            dfree(h, &h->rt_uniq, dalloc_bytes(E, 8));
-            dfree(h, &h->rt_cnt, dalloc_bytes(E, 4));
-            dfree(h, &h->rt_cur, dalloc_bytes(2, 8));
-            return rc;
-        }
-        h->rt_cub = cub8;
-        h->rt_cub_bytes = cb;
-        h->rt_exc_cap = E;
-    }
+    if (int rc = route_exc_scratch(h, h->NL)) return rc;
     const swimsim::RouteTable *tab = nullptr;
     int rc = 0;
     if ((rc = route_grow(h, &h->rt_rows, &h->rt_rows_cap, 1, "route rows"))) return rc;
@@ -3428,6 +3452,217 @@ int swimsim_route_census(swimsim_t *h, const uint8_t *keys, const uint64_t *off,
                 put((int32_t)o1 - 1, rcnt[i]);
             }
             if (!placed) put(base[k], bc);
+        }
+        kb = ke;
+    }
+    hist_off[nkeys] = total;
+    *nhist = total;
+    if (ms) *ms = total_ms;
+    return SWIMSIM_OK;
+}
+
+// ---- replica sets through the observers' ring views (k_route_n) ----
+namespace {
+
+int route_n_check(swimsim *h, uint32_t n, const char *who) {
+    if (n < 1 || n > ROUTE_NN_MAX) return h->fail(SWIMSIM_EINVAL, "%s: n %u not in 1..%u", who, n, ROUTE_NN_MAX);
+    return 0;
+}
+
+// k_route_n holds ROUTE_N_STATIC_LDS bytes beside the bitmap: past the default 64 KB the dynamic part must be allowed
+int route_n_lds(swimsim *h) {
+    if ((size_t)route_bitmap_bytes(h->NP) + ROUTE_N_STATIC_LDS > 65536) {
+        HIPCHK(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_route_n<false>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                      (int)route_bitmap_bytes(h->NP)));
+        HIPCHK(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_route_n<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                      (int)route_bitmap_bytes(h->NP)));
+    }
+    return 0;
+}
+
+}  // namespace
+
+int swimsim_route_n(swimsim_t *h, const uint8_t *keys, const uint64_t *off, size_t nkeys, uint32_t replica_points, uint32_t n,
+                    const uint32_t *observers, size_t nobs, int32_t mode, int32_t *prefs, uint32_t *servers, double *ms) {
+    if (!h) return SWIMSIM_EINVAL;
+    if (!prefs) return h->fail(SWIMSIM_EINVAL, "route_n: no output buffer");
+    if (int rc = route_check(h, keys, off, nkeys, replica_points, mode, "route_n")) return rc;
+    if (int rc = route_n_check(h, n, "route_n")) return rc;
+    if (!observers || nobs == 0) return h->fail(SWIMSIM_EINVAL, "route_n: no observers");
+    for (size_t j = 0; j < nobs; j++)
+        if (observers[j] < h->lo || observers[j] >= h->lo + h->NL)
+            return h->fail(SWIMSIM_EINVAL, "route_n: observer %u is not a row of this handle", observers[j]);
+    if (nobs > 0xFFFFFFFFull) return h->fail(SWIMSIM_EINVAL, "route_n: list of %zu observers too long", nobs);
+    DeviceScope ds(h->device);
+    const swimsim::RouteTable *tab = nullptr;
+    const size_t per_key = nkeys * n;                                // words of one row's lists
+    const size_t per = std::max<size_t>(1, std::min(nobs, ROUTE_OWN_WORDS / per_key));   // rows per launch
+    int rc = 0;
+    if ((rc = route_grow(h, &h->rt_rows, &h->rt_rows_cap, nobs, "route rows")) ||
+        (rc = route_grow(h, &h->rt_srv, &h->rt_srv_cap, nobs, "route server counts")) ||
+        (rc = route_grow(h, &h->rt_own, &h->rt_own_cap, per * per_key, "route owners")))
+        return rc;
+    if ((rc = route_keys(h, keys, off, nkeys, replica_points, &tab)) || (rc = route_n_lds(h))) return rc;
+    std::vector<uint32_t> rows(nobs);
+    for (size_t j = 0; j < nobs; j++) rows[j] = observers[j] - h->lo;
+    HIPCHK(h, hipMemcpyAsync(h->rt_rows, rows.data(), nobs * 4, hipMemcpyHostToDevice, h->s));
+    RouteNArgs a{};
+    a.r = route_args(h, tab, nkeys, mode);
+    a.n = n;
+    a.prefs = h->rt_own;
+    for (size_t j0 = 0; j0 < nobs; j0 += per) {
+        const size_t nr = std::min(per, nobs - j0);
+        a.r.rows = h->rt_rows + j0;
+        a.servers = h->rt_srv + j0;
+        hipLaunchKernelGGL(k_route_n<false>, dim3((uint32_t)nr), dim3(ROUTE_THREADS), route_bitmap_bytes(h->NP), h->s, h->d, a);
+        if (j0 + per >= nobs) HIPCHK(h, hipEventRecord(h->rt_ev[1], h->s));
+        HIPCHK(h, hipMemcpyAsync(prefs + j0 * per_key, h->rt_own, nr * per_key * 4, hipMemcpyDeviceToHost, h->s));
+    }
+    if (servers) HIPCHK(h, hipMemcpyAsync(servers, h->rt_srv, nobs * 4, hipMemcpyDeviceToHost, h->s));
+    HIPCHK(h, stream_sync(h));
+    HIPCHK(h, hipGetLastError());
+    if (ms) {
+        float t = 0;
+        HIPCHK(h, hipEventElapsedTime(&t, h->rt_ev[0], h->rt_ev[1]));
+        *ms = t;
+    }
+    return SWIMSIM_OK;
+}
+
+int swimsim_replica_census(swimsim_t *h, const uint8_t *keys, const uint64_t *off, size_t nkeys, uint32_t replica_points, uint32_t n,
+                           int32_t who, int32_t mode, uint32_t *counted, uint64_t *hist_off, int32_t *hist_member,
+                           uint32_t *hist_count, size_t cap, size_t *nhist, double *ms) {
+    if (!h) return SWIMSIM_EINVAL;
+    if (!counted || !hist_off || !nhist || (cap && (!hist_member || !hist_count)))
+        return h->fail(SWIMSIM_EINVAL, "replica census: no output buffer");
+    if (int rc = route_check(h, keys, off, nkeys, replica_points, mode, "replica census")) return rc;
+    if (int rc = route_n_check(h, n, "replica census")) return rc;
+    if (who != SWIMSIM_CENSUS_LIVE && who != SWIMSIM_CENSUS_ALL) return h->fail(SWIMSIM_EINVAL, "replica census: unknown who %d", who);
+    DeviceScope ds(h->device);
+    const uint32_t all = who == SWIMSIM_CENSUS_ALL;
+    uint32_t first = SRC_NONE, ncount = 0;                           // (the host keeps the live table: swimsim_route_census)
+    for (uint32_t r = 0; r < h->NL; r++)
+        if (all || h->live[h->lo + r]) {
+            if (first == SRC_NONE) first = r;
+            ncount++;
+        }
+    *counted = ncount;
+    *nhist = 0;
+    if (ms) *ms = 0;
+    if (ncount == 0) {                                               // no row counts: no entry for any key
+        for (size_t k = 0; k <= nkeys; k++) hist_off[k] = 0;
+        return SWIMSIM_OK;
+    }
+    // A row appends, per key, at most n members its set has beyond the base and n the base has beyond its set: a pass
+    // over one key appends at most 2n * NL pairs, so a buffer of at least 2n * NL pairs always ends the chunking below
+    int rc = 0;
+    if ((rc = route_exc_scratch(h, (size_t)2 * n * h->NL))) return rc;
+    const swimsim::RouteTable *tab = nullptr;
+    if ((rc = route_grow(h, &h->rt_rows, &h->rt_rows_cap, 1, "route rows")) ||
+        (rc = route_grow(h, &h->rt_nbase, &h->rt_nbase_cap, nkeys * n, "route base sets")))
+        return rc;
+    if ((rc = route_keys(h, keys, off, nkeys, replica_points, &tab)) || (rc = route_n_lds(h))) return rc;
+    double total_ms = 0;
+    float t = 0;
+    // nbase[k][*]: the set under the first counted row
+    HIPCHK(h, hipMemcpyAsync(h->rt_rows, &first, 4, hipMemcpyHostToDevice, h->s));
+    RouteNArgs a{};
+    a.r = route_args(h, tab, nkeys, mode);
+    a.n = n;
+    a.r.rows = h->rt_rows;
+    a.prefs = h->rt_nbase;
+    hipLaunchKernelGGL(k_route_n<false>, dim3(1), dim3(ROUTE_THREADS), route_bitmap_bytes(h->NP), h->s, h->d, a);
+    std::vector<int32_t> base(nkeys * n);
+    HIPCHK(h, hipMemcpyAsync(base.data(), h->rt_nbase, nkeys * n * 4, hipMemcpyDeviceToHost, h->s));
+    a.prefs = nullptr;
+    a.r.rows = nullptr;
+    a.nbase = h->rt_nbase;
+    a.r.skip_row = first;
+    a.r.all = all;
+    a.r.exc = h->rt_exc;
+    a.r.cursor = h->rt_cur;
+    a.r.exc_cap = h->rt_exc_cap;
+    uint32_t *nruns_d = reinterpret_cast<uint32_t *>(h->rt_cur + 1);
+    std::vector<unsigned long long> runs;
+    std::vector<uint32_t> rcnt;
+    size_t total = 0, kb = 0, chunk = nkeys;
+    bool first_pass = true;
+    while (kb < nkeys) {
+        const size_t ke = std::min(nkeys, kb + chunk);
+        a.r.k0 = (uint32_t)kb;
+        a.r.k1 = (uint32_t)ke;
+        HIPCHK(h, hipMemsetAsync(h->rt_cur, 0, 16, h->s));
+        if (!first_pass) HIPCHK(h, hipEventRecord(h->rt_ev[0], h->s));   // (the first pass's time includes the keys and the base)
+        hipLaunchKernelGGL(k_route_n<true>, dim3(h->NL), dim3(ROUTE_THREADS), route_bitmap_bytes(h->NP), h->s, h->d, a);
+        HIPCHK(h, hipEventRecord(h->rt_ev[1], h->s));
+        unsigned long long cur = 0;
+        HIPCHK(h, hipMemcpyAsync(&cur, h->rt_cur, 8, hipMemcpyDeviceToHost, h->s));
+        HIPCHK(h, stream_sync(h));                                   // the pass's host synchronisation
+        HIPCHK(h, hipGetLastError());
+        first_pass = false;
+        HIPCHK(h, hipEventElapsedTime(&t, h->rt_ev[0], h->rt_ev[1]));
+        total_ms += t;
+        if (cur > h->rt_exc_cap) {                                   // the buffer was full: nothing of this pass is used
+            if (ke - kb == 1)
+                return h->fail(SWIMSIM_EHIP, "replica census: %llu exceptions of one key over %u rows, n = %u", cur, h->NL, n);
+            chunk = std::max<size_t>(1, (ke - kb) / 2);
+            continue;
+        }
+        size_t nr = 0;
+        if (cur) {                                                   // sort the pairs, count the runs of equal pairs
+            HIPCHK(h, hipEventRecord(h->rt_ev[0], h->s));
+            hipcub::DoubleBuffer<unsigned long long> db(h->rt_exc, h->rt_exc2);
+            HIPCHK(h, hipcub::DeviceRadixSort::SortKeys(h->rt_cub, h->rt_cub_bytes, db, (int)cur, 0, 64, h->s));
+            HIPCHK(h, hipcub::DeviceRunLengthEncode::Encode(h->rt_cub, h->rt_cub_bytes, db.Current(), h->rt_uniq, h->rt_cnt, nruns_d,
+                                                           (int)cur, h->s));
+            HIPCHK(h, hipEventRecord(h->rt_ev[1], h->s));
+            uint32_t nruns = 0;
+            const size_t spec = std::min<size_t>(cur, ROUTE_RUNS_FIRST);
+            runs.resize(spec);
+            rcnt.resize(spec);
+            HIPCHK(h, hipMemcpyAsync(&nruns, nruns_d, 4, hipMemcpyDeviceToHost, h->s));
+            HIPCHK(h, hipMemcpyAsync(runs.data(), h->rt_uniq, spec * 8, hipMemcpyDeviceToHost, h->s));
+            HIPCHK(h, hipMemcpyAsync(rcnt.data(), h->rt_cnt, spec * 4, hipMemcpyDeviceToHost, h->s));
+            HIPCHK(h, stream_sync(h));
+            HIPCHK(h, hipEventElapsedTime(&t, h->rt_ev[0], h->rt_ev[1]));
+            total_ms += t;
+            nr = nruns;
+            if (nr > spec) {
+                runs.resize(nr);
+                rcnt.resize(nr);
+                HIPCHK(h, hipMemcpyAsync(runs.data() + spec, h->rt_uniq + spec, (nr - spec) * 8, hipMemcpyDeviceToHost, h->s));
+                HIPCHK(h, hipMemcpyAsync(rcnt.data() + spec, h->rt_cnt + spec, (nr - spec) * 4, hipMemcpyDeviceToHost, h->s));
+                HIPCHK(h, stream_sync(h));
+            }
+        }
+        // the histogram of keys [kb, ke): the runs are ascending by (key, member, sign). A base member is listed by every
+        // counted row but those of its sign-1 run; any other member by the rows of its sign-0 run
+        size_t i = 0;
+        auto put = [&](int32_t member, uint32_t c) {
+            if (c == 0) return;
+            if (total < cap) {
+                hist_member[total] = member;
+                hist_count[total] = c;
+            }
+            total++;
+        };
+        int32_t bs[ROUTE_NN_MAX];
+        for (size_t k = kb; k < ke; k++) {
+            hist_off[k] = total;
+            uint32_t nb = 0, bi = 0;
+            for (uint32_t j = 0; j < n && base[k * n + j] >= 0; j++) bs[nb++] = base[k * n + j];
+            std::sort(bs, bs + nb);
+            for (; i < nr && (runs[i] >> 32) == k; i++) {
+                const int32_t m = (int32_t)(((uint32_t)runs[i]) >> 1) - 1;
+                while (bi < nb && bs[bi] < m) put(bs[bi++], ncount);
+                if (bi < nb && bs[bi] == m) {                        // (its run has sign 1)
+                    put(m, ncount - rcnt[i]);
+                    bi++;
+                } else {
+                    put(m, rcnt[i]);
+                }
+            }
+            while (bi < nb) put(bs[bi++], ncount);
         }
         kb = ke;
     }

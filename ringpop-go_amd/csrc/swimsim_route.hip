@@ -25,6 +25,7 @@
 //                   appends what its waves hold with one cursor bump at the end (a wave whose buffer fills flushes
 //                   alone, one bump per wave). The host sorts and run-length encodes the pairs, so the result does
 //                   not depend on the order of arrival.
+//   k_route_n       the same two stages, then LookupN per key: the n distinct owners in walk order (below).
 // The kernels only read mw and live, on the main stream (as the census).
 #pragma once
 #include "swimsim_device.h"
@@ -119,27 +120,10 @@ __device__ __forceinline__ void route_flush(const RouteArgs &a, const unsigned l
         if (at + i < a.exc_cap) a.exc[at + i] = stage[i];
 }
 
-// route: grid = routed rows; census: grid = NL (workgroups of rows that do not count return at once).
-// Dynamic LDS: route_bitmap_bytes(NP).
-template <bool CENSUS>
-__global__ void __launch_bounds__(ROUTE_THREADS) k_route(DS d, RouteArgs a) {
-    extern __shared__ unsigned long long route_bm[];
-    __shared__ uint32_t list[ROUTE_LIST_CAP];
-    __shared__ uint32_t tpre[ROUTE_THREADS];
-    __shared__ uint32_t wcnt[ROUTE_THREADS / 64];
-    __shared__ unsigned long long xbuf[ROUTE_THREADS / 64][ROUTE_STAGE];   // census: each wave's exception pairs
-    __shared__ uint32_t xcnt[ROUTE_THREADS / 64];
-    __shared__ unsigned long long xat;
+// Stage 1 of a routed row (the whole workgroup, ROUTE_THREADS threads): stream the row's words and ballot status <= suspect
+// into the presence bitmap route_bm (route_bitmap_bytes(NP) of LDS). Returns cnt, the row's servers. wcnt: ROUTE_THREADS / 64 words.
+__device__ __forceinline__ uint32_t route_stage_bitmap(const DS &d, uint32_t row, unsigned long long *route_bm, uint32_t *wcnt) {
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-    uint32_t row;
-    if (CENSUS) {
-        row = blockIdx.x;
-        if (row == a.skip_row || !(a.all || d.live[d.lo + row])) return;      // (the whole workgroup)
-    } else {
-        row = a.rows[blockIdx.x];
-    }
-    if (row >= d.NL) return;
-    // ---- 1. the presence bitmap of the row ----
     const uint32_t *rowp = d.mw + (size_t)row * d.NP;
     const uint32_t ngroups = route_groups(d.NP);
     uint32_t cntw = 0;
@@ -170,44 +154,75 @@ __global__ void __launch_bounds__(ROUTE_THREADS) k_route(DS d, RouteArgs a) {
     uint32_t cnt = 0;
 #pragma unroll
     for (uint32_t v = 0; v < ROUTE_THREADS / 64; v++) cnt += wcnt[v];
+    return cnt;
+}
+
+// Stage 2 (the whole workgroup): the present members as a list in LDS, ascending, as far as ROUTE_LIST_CAP goes.
+// tpre: ROUTE_THREADS words.
+__device__ __forceinline__ void route_stage_list(const DS &d, const unsigned long long *route_bm, uint32_t *list, uint32_t *tpre) {
+    const uint32_t tid = threadIdx.x;
+    const uint32_t ngroups = route_groups(d.NP);
+    const uint32_t gper = (ngroups + ROUTE_THREADS - 1) / ROUTE_THREADS;
+    const uint32_t gs = min(tid * gper, ngroups), ge = min(gs + gper, ngroups);
+    uint32_t mine = 0;
+    for (uint32_t g = gs; g < ge; g++)
+        mine += (uint32_t)(__popcll(route_bm[g * 4u]) + __popcll(route_bm[g * 4u + 1]) + __popcll(route_bm[g * 4u + 2]) +
+                           __popcll(route_bm[g * 4u + 3]));
+    tpre[tid] = mine;
+    __syncthreads();
+    if (tid == 0) {
+        uint32_t run = 0;
+        for (uint32_t t = 0; t < ROUTE_THREADS; t++) {
+            const uint32_t c = tpre[t];
+            tpre[t] = run;
+            run += c;
+        }
+    }
+    __syncthreads();
+    uint32_t at = tpre[tid];
+    for (uint32_t g = gs; g < ge; g++) {
+        const unsigned long long b0 = route_bm[g * 4u], b1 = route_bm[g * 4u + 1], b2 = route_bm[g * 4u + 2],
+                                 b3 = route_bm[g * 4u + 3];
+        unsigned long long any = b0 | b1 | b2 | b3;
+        while (any) {
+            const uint32_t l = (uint32_t)__builtin_ctzll(any);
+            any &= any - 1;
+            const uint32_t m = g * ROUTE_GROUP + l * 4u;
+            if ((b0 >> l) & 1ull) { if (at < ROUTE_LIST_CAP) list[at] = m; at++; }
+            if ((b1 >> l) & 1ull) { if (at < ROUTE_LIST_CAP) list[at] = m + 1; at++; }
+            if ((b2 >> l) & 1ull) { if (at < ROUTE_LIST_CAP) list[at] = m + 2; at++; }
+            if ((b3 >> l) & 1ull) { if (at < ROUTE_LIST_CAP) list[at] = m + 3; at++; }
+        }
+    }
+    __syncthreads();
+}
+
+// route: grid = routed rows; census: grid = NL (workgroups of rows that do not count return at once).
+// Dynamic LDS: route_bitmap_bytes(NP).
+template <bool CENSUS>
+__global__ void __launch_bounds__(ROUTE_THREADS) k_route(DS d, RouteArgs a) {
+    extern __shared__ unsigned long long route_bm[];
+    __shared__ uint32_t list[ROUTE_LIST_CAP];
+    __shared__ uint32_t tpre[ROUTE_THREADS];
+    __shared__ uint32_t wcnt[ROUTE_THREADS / 64];
+    __shared__ unsigned long long xbuf[ROUTE_THREADS / 64][ROUTE_STAGE];   // census: each wave's exception pairs
+    __shared__ uint32_t xcnt[ROUTE_THREADS / 64];
+    __shared__ unsigned long long xat;
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    uint32_t row;
+    if (CENSUS) {
+        row = blockIdx.x;
+        if (row == a.skip_row || !(a.all || d.live[d.lo + row])) return;      // (the whole workgroup)
+    } else {
+        row = a.rows[blockIdx.x];
+    }
+    if (row >= d.NL) return;
+    // ---- 1. the presence bitmap of the row ----
+    const uint32_t cnt = route_stage_bitmap(d, row, route_bm, wcnt);
     // ---- 2. sparse rows: the present members as a list, ascending ----
     const bool direct = cnt != 0 && cnt <= ROUTE_LIST_CAP &&
                         (a.mode == 2u || (a.mode == 0u && (uint64_t)cnt * cnt * a.R <= d.N));
-    if (direct) {                                                      // (the whole workgroup)
-        const uint32_t gper = (ngroups + ROUTE_THREADS - 1) / ROUTE_THREADS;
-        const uint32_t gs = min(tid * gper, ngroups), ge = min(gs + gper, ngroups);
-        uint32_t mine = 0;
-        for (uint32_t g = gs; g < ge; g++)
-            mine += (uint32_t)(__popcll(route_bm[g * 4u]) + __popcll(route_bm[g * 4u + 1]) + __popcll(route_bm[g * 4u + 2]) +
-                               __popcll(route_bm[g * 4u + 3]));
-        tpre[tid] = mine;
-        __syncthreads();
-        if (tid == 0) {
-            uint32_t run = 0;
-            for (uint32_t t = 0; t < ROUTE_THREADS; t++) {
-                const uint32_t c = tpre[t];
-                tpre[t] = run;
-                run += c;
-            }
-        }
-        __syncthreads();
-        uint32_t at = tpre[tid];
-        for (uint32_t g = gs; g < ge; g++) {
-            const unsigned long long b0 = route_bm[g * 4u], b1 = route_bm[g * 4u + 1], b2 = route_bm[g * 4u + 2],
-                                     b3 = route_bm[g * 4u + 3];
-            unsigned long long any = b0 | b1 | b2 | b3;
-            while (any) {
-                const uint32_t l = (uint32_t)__builtin_ctzll(any);
-                any &= any - 1;
-                const uint32_t m = g * ROUTE_GROUP + l * 4u;
-                if ((b0 >> l) & 1ull) { if (at < ROUTE_LIST_CAP) list[at] = m; at++; }
-                if ((b1 >> l) & 1ull) { if (at < ROUTE_LIST_CAP) list[at] = m + 1; at++; }
-                if ((b2 >> l) & 1ull) { if (at < ROUTE_LIST_CAP) list[at] = m + 2; at++; }
-                if ((b3 >> l) & 1ull) { if (at < ROUTE_LIST_CAP) list[at] = m + 3; at++; }
-            }
-        }
-        __syncthreads();
-    }
+    if (direct) route_stage_list(d, route_bm, list, tpre);             // (the whole workgroup)
     // ---- 3. one thread per key ----
     const unsigned long long below = (1ull << lane) - 1ull;
     uint32_t nx = 0;                                                   // census: pairs staged by this wave (wave-uniform)
@@ -251,6 +266,192 @@ __global__ void __launch_bounds__(ROUTE_THREADS) k_route(DS d, RouteArgs a) {
                     route_flush(a, xbuf[wave], nx, route_bump(a.cursor, nx, lane), lane);
                     route_fence_lanes();
                     nx = 0;
+                }
+            }
+        }
+    }
+    if (CENSUS) {                                                      // what the waves still hold: one bump per workgroup
+        if (lane == 0) xcnt[wave] = nx;
+        __syncthreads();
+        if (tid == 0) {
+            uint32_t tot = 0;
+#pragma unroll
+            for (uint32_t v = 0; v < ROUTE_THREADS / 64; v++) tot += xcnt[v];
+            xat = tot ? atomicAdd(a.cursor, (unsigned long long)tot) : 0ull;
+        }
+        __syncthreads();
+        unsigned long long at = xat;
+        for (uint32_t v = 0; v < wave; v++) at += xcnt[v];
+        route_flush(a, xbuf[wave], nx, at, lane);
+    }
+}
+
+// ---- replica sets: LookupN through every observer's view (swimsim_route_n / swimsim_replica_census) ----
+//
+// prefs(o, k, n): the n distinct owners the view ring of observer o meets from the first REAL point >= Fingerprint32(k),
+// wrapping once, each at its first occurrence; a view of cnt <= n servers lists all of them in ascending member index
+// (include/swimsim.h). A point is real only for the lowest present member at its hash: pts and hm hold an entry for
+// every member, so when present members a < b share a hash, b's entry is no point of this view and must not list b.
+//   k_route_n   stages 1 and 2 of k_route (the presence bitmap, the ascending list), then one thread per key:
+//     cnt <= n  the list itself (n <= ROUTE_NN_MAX <= ROUTE_LIST_CAP: such a row always fits the list);
+//     walk      from p0 along pts, the whole 8-byte point. A point whose member is present is taken unless its hash
+//               equals the hash of the last present point seen (equal hashes are contiguous in pts, member ascending,
+//               and p0 is a lower bound, so a run is never entered in its middle: the first present entry of a run is
+//               the real point, every later present entry a duplicate, whether or not the first one's member was new),
+//               and unless its member is already collected. Stops at n members, at most P steps, one wrap;
+//     direct    the same walk over the listed members' own replica hashes: each step takes the minimum of
+//               ((hm[m][i] - h) mod 2^32) << 32 | m above the last one taken, over ALL listed members (collected ones
+//               too: a collected member's entry at a shared hash is what marks the higher member's entry a
+//               duplicate), cnt * R compares per step. Walk and direct visit the same present points, so the
+//               ratio of their costs is ABI 9's: direct while cnt * cnt * R <= N.
+//   The collected members of a thread are n words of LDS, coll[i * ROUTE_THREADS + tid] (16 KB at n = 16: with the
+//   64 KB bitmap of N = 524,288, the list, the prefix and the stage that is 87 KB of a CU's 160 KB).
+//   Census: base[k * n + i] is the set under the first counted row. A lane whose set differs stages
+//   key << 32 | (member + 1) << 1 | sign for every member of its set that is not in the base (sign 0) and every base
+//   member that is not in its set (sign 1): up to 2n pairs per key and row. The pairs of a key step are staged slot by
+//   slot (2n ballots, each adds up to 64 pairs to the wave's buffer, which flushes when another 64 would not fit), so
+//   ROUTE_STAGE holds as it is. A pass over ONE key appends at most 2n * NL pairs: the host sizes the buffer to at
+//   least that, so that halving the keys of an overflowing pass always ends (swimsim_replica_census).
+constexpr uint32_t ROUTE_NN_MAX = 16;              // replicas per key at most (the n of LookupN)
+static_assert(ROUTE_NN_MAX <= ROUTE_LIST_CAP && 2 * ROUTE_NN_MAX <= 32, "a row of cnt <= n fits the list; 2n slot bits");
+// static LDS of k_route_n (the dynamic bitmap comes on top): coll, list, tpre, xbuf and the small words
+constexpr uint32_t ROUTE_N_STATIC_LDS = ROUTE_NN_MAX * ROUTE_THREADS * 4 + ROUTE_LIST_CAP * 4 + ROUTE_THREADS * 4 +
+                                        (ROUTE_THREADS / 64) * ROUTE_STAGE * 8 + 64;
+
+struct RouteNArgs {
+    RouteArgs r;                     // owners, base and K are not used
+    uint32_t n;                      // 1..ROUTE_NN_MAX
+    int32_t *prefs;                  // route: prefs[(b * K + k) * n + i], -1 past min(n, cnt)
+    uint32_t *servers;               // route: servers[b] = cnt
+    const int32_t *nbase;            // census: [K][n] the set under the first counted row, -1 past min(n, cnt)
+};
+
+// route: grid = routed rows; census: grid = NL. Dynamic LDS: route_bitmap_bytes(NP).
+template <bool CENSUS>
+__global__ void __launch_bounds__(ROUTE_THREADS) k_route_n(DS d, RouteNArgs an) {
+    extern __shared__ unsigned long long route_bm[];
+    __shared__ uint32_t coll[ROUTE_NN_MAX * ROUTE_THREADS];
+    __shared__ uint32_t list[ROUTE_LIST_CAP];
+    __shared__ uint32_t tpre[ROUTE_THREADS];
+    __shared__ uint32_t wcnt[ROUTE_THREADS / 64];
+    __shared__ unsigned long long xbuf[ROUTE_THREADS / 64][ROUTE_STAGE];
+    __shared__ uint32_t xcnt[ROUTE_THREADS / 64];
+    __shared__ unsigned long long xat;
+    const RouteArgs &a = an.r;
+    const uint32_t n = an.n;
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    uint32_t row;
+    if (CENSUS) {
+        row = blockIdx.x;
+        if (row == a.skip_row || !(a.all || d.live[d.lo + row])) return;      // (the whole workgroup)
+    } else {
+        row = a.rows[blockIdx.x];
+    }
+    if (row >= d.NL) return;
+    const uint32_t cnt = route_stage_bitmap(d, row, route_bm, wcnt);
+    const bool small = cnt <= n;                                       // every server, ascending: the list
+    const bool direct = !small && cnt <= ROUTE_LIST_CAP && (a.mode == 2u || (a.mode == 0u && (uint64_t)cnt * cnt * a.R <= d.N));
+    if (cnt != 0 && (small || direct)) route_stage_list(d, route_bm, list, tpre);   // (the whole workgroup)
+    if (!CENSUS && tid == 0 && an.servers) an.servers[blockIdx.x] = cnt;
+    const uint32_t want = min(n, cnt);
+    uint32_t *mine = coll + tid;                                       // member i of this thread: mine[i * ROUTE_THREADS]
+    const unsigned long long below = (1ull << lane) - 1ull;
+    uint32_t nx = 0;                                                   // census: pairs staged by this wave (wave-uniform)
+    for (uint32_t kb = a.k0; kb < a.k1; kb += ROUTE_THREADS) {
+        const uint32_t k = kb + tid;
+        const bool valid = k < a.k1;
+        uint32_t got = 0;
+        if (valid && cnt) {
+            const uint32_t h = a.kh[k];
+            if (small) {
+                for (; got < cnt; got++) mine[got * ROUTE_THREADS] = list[got];
+            } else if (direct) {
+                unsigned long long cur = 0;                            // the last (distance, member) taken
+                bool first = true;
+                uint32_t lastd = 0;
+                for (uint32_t step = 0; step < a.P && got < want; step++) {
+                    unsigned long long best = ~0ull;
+                    for (uint32_t j = 0; j < cnt; j++) {
+                        const uint32_t m = (uint32_t)__builtin_amdgcn_readfirstlane((int)list[j]);   // (j is the same in every active lane)
+                        const uint32_t *hp = a.hm + (size_t)m * a.R;
+                        for (uint32_t i = 0; i < a.R; i++) {
+                            const unsigned long long v = ((unsigned long long)(hp[i] - h) << 32) | m;
+                            if ((first || v > cur) && v < best) best = v;
+                        }
+                    }
+                    if (best == ~0ull) break;                          // every entry was visited
+                    const uint32_t dist = (uint32_t)(best >> 32), m = (uint32_t)best;
+                    const bool dup = !first && dist == lastd;          // a higher member's entry at the same hash
+                    cur = best; first = false; lastd = dist;
+                    if (!dup) {
+                        bool seen = false;
+                        for (uint32_t q = 0; q < got; q++) seen |= mine[q * ROUTE_THREADS] == m;
+                        if (!seen) mine[got++ * ROUTE_THREADS] = m;
+                    }
+                }
+            } else {
+                uint32_t p = a.p0[k], lasth = 0;
+                bool any = false;                                      // a present point was seen: lasth holds its hash
+                for (uint32_t step = 0; step < a.P && got < want; step++, p++) {
+                    if (p >= a.P) p = 0;
+                    const unsigned long long pt = a.pts[p];
+                    const uint32_t m = (uint32_t)pt, ph = (uint32_t)(pt >> 32);
+                    if (!route_present(route_bm, m)) continue;
+                    const bool dup = any && ph == lasth;
+                    any = true; lasth = ph;
+                    if (dup) continue;
+                    bool seen = false;
+                    for (uint32_t q = 0; q < got; q++) seen |= mine[q * ROUTE_THREADS] == m;
+                    if (!seen) mine[got++ * ROUTE_THREADS] = m;
+                }
+            }
+        }
+        if (!CENSUS) {
+            if (valid) {
+                int32_t *out = an.prefs + ((size_t)blockIdx.x * a.K + k) * n;
+                for (uint32_t i = 0; i < n; i++) out[i] = i < got ? (int32_t)mine[i * ROUTE_THREADS] : -1;
+            }
+        } else {
+            uint32_t plus = 0, minus = 0;                              // bit i: my member i is not in the base; base member i not mine
+            const int32_t *bp = an.nbase + (size_t)(valid ? k : a.k0) * n;
+            if (valid) {
+                bool same = true;
+                for (uint32_t i = 0; i < n; i++) same &= bp[i] == (i < got ? (int32_t)mine[i * ROUTE_THREADS] : -1);
+                if (!same) {                                           // (equal lists are equal sets: the common case)
+                    for (uint32_t i = 0; i < got; i++) {
+                        const int32_t m = (int32_t)mine[i * ROUTE_THREADS];
+                        bool in = false;
+                        for (uint32_t j = 0; j < n; j++) in |= bp[j] == m;
+                        if (!in) plus |= 1u << i;
+                    }
+                    for (uint32_t j = 0; j < n; j++) {
+                        const int32_t b = bp[j];
+                        if (b < 0) break;                              // (the base's -1 slots are its last)
+                        bool in = false;
+                        for (uint32_t i = 0; i < got; i++) in |= (int32_t)mine[i * ROUTE_THREADS] == b;
+                        if (!in) minus |= 1u << j;
+                    }
+                }
+            }
+            if (__ballot((plus | minus) != 0u)) {                      // (wave-uniform)
+                for (uint32_t s = 0; s < 2u * n; s++) {
+                    const bool sign = s >= n;
+                    const uint32_t i = sign ? s - n : s;
+                    const bool is = ((sign ? minus : plus) >> i) & 1u;
+                    const unsigned long long mask = __ballot(is);
+                    if (!mask) continue;                               // (wave-uniform; nx <= ROUTE_STAGE - 64 here)
+                    if (is) {
+                        const uint32_t m = sign ? (uint32_t)bp[i] : mine[i * ROUTE_THREADS];
+                        xbuf[wave][nx + (uint32_t)__popcll(mask & below)] =
+                            ((unsigned long long)k << 32) | ((unsigned long long)(m + 1u) << 1) | (sign ? 1ull : 0ull);
+                    }
+                    nx += (uint32_t)__popcll(mask);
+                    if (nx > ROUTE_STAGE - 64) {                       // no room for another slot: the wave flushes alone
+                        route_fence_lanes();
+                        route_flush(a, xbuf[wave], nx, route_bump(a.cursor, nx, lane), lane);
+                        route_fence_lanes();
+                        nx = 0;
+                    }
                 }
             }
         }

@@ -37,6 +37,7 @@ COUNTER_NAMES = [
 T0_MS = 1_500_000_000_000
 CENSUS_LIVE, CENSUS_ALL = 0, 1                   # swimsim_census `who`
 CENSUS_WHO = {"live": CENSUS_LIVE, "all": CENSUS_ALL}
+ROUTE_N_REPLICAS = 16                            # swimsim_route_n / swimsim_replica_census: n is 1..16
 CENSUS_STATUSES = ("alive", "suspect", "faulty", "leave", "tombstone", "unknown")   # columns of a census count
 ERRORS = {-1: "EINVAL", -2: "ENOMEM", -3: "EHIP", -4: "ECAPACITY", -5: "ERANGE"}
 
@@ -191,6 +192,9 @@ def load_library(path: str = LIB_PATH):
         "swimsim_route": (C.c_int, [P, P, P, sz, u32, P, sz, i32, P, C.POINTER(C.c_double)]),
         "swimsim_route_census": (C.c_int, [P, P, P, sz, u32, i32, i32, C.POINTER(u32), P, P, P, sz, C.POINTER(sz),
                                            C.POINTER(C.c_double)]),
+        "swimsim_route_n": (C.c_int, [P, P, P, sz, u32, u32, P, sz, i32, P, P, C.POINTER(C.c_double)]),
+        "swimsim_replica_census": (C.c_int, [P, P, P, sz, u32, u32, i32, i32, C.POINTER(u32), P, P, P, sz, C.POINTER(sz),
+                                             C.POINTER(C.c_double)]),
     }
     for name, (res, args) in sigs.items():
         f = getattr(L, name)
@@ -269,9 +273,17 @@ def _census_who(who, what):
     return int(w)
 
 
+def _replica_n(n, what):
+    """the replica count of route_n / replica_census, refused here when it is outside 1..ROUTE_N_REPLICAS"""
+    if isinstance(n, bool) or int(n) != n or not 1 <= int(n) <= ROUTE_N_REPLICAS:
+        raise ValueError(f"{what}: n is 1..{ROUTE_N_REPLICAS}, not {n!r}")
+    return int(n)
+
+
 def merge_route_histograms(parts):
     """add per-shard route_census results (counted, hist_off, hist_owner, hist_count, ms) per (key, owner): the
-    histogram of the union of the shards' rows, in the same layout (owners ascending per key, -1 first)"""
+    histogram of the union of the shards' rows, in the same layout (owners ascending per key, -1 first). The results
+    of replica_census add the same way, per (key, member)."""
     K = len(parts[0][1]) - 1
     counted = sum(int(p[0]) for p in parts)
     key = np.concatenate([np.repeat(np.arange(K, dtype=np.int64), np.diff(p[1]).astype(np.int64)) for p in parts])
@@ -648,6 +660,48 @@ class Cluster:
                 return counted.value, hoff, own[:nh.value].copy(), cnt[:nh.value].copy(), ms.value
             cap = nh.value
 
+    # ---- replica sets through the observers' own ring views (swimsim_route_n / swimsim_replica_census) ----
+    def route_n(self, keys, observers, n=3, replica_points=100, mode=0):
+        """(prefs int32 [nobs, K, n], servers uint32 [nobs]): prefs[j, k] lists the members that hold key k by the
+        ring of observer observers[j] (Ringpop.LookupN), in the order the ring walk meets them; a view of
+        servers[j] <= n members lists all of them in ascending index, and the unused slots are -1. n is 1..16; keys,
+        observers and mode as for route()."""
+        n = _replica_n(n, "route_n")
+        blob, off = _pack_keys(keys)
+        obs = _member_list(observers)
+        out = np.empty((len(obs), len(off) - 1, n), np.int32)
+        srv = np.empty(len(obs), np.uint32)
+        ms = C.c_double()
+        self._chk(load_library().swimsim_route_n(self.h, blob, off.ctypes.data, len(off) - 1, int(replica_points), n,
+                                                 obs.ctypes.data if len(obs) else None, len(obs), int(mode),
+                                                 out.ctypes.data, srv.ctypes.data, C.byref(ms)))
+        self.last_route_ms = ms.value
+        return out, srv
+
+    def replica_census(self, keys, n=3, who="live", replica_points=100, mode=0):
+        """(counted, hist_off[K + 1], hist_member, hist_count, ms): for key k, hist_member / hist_count
+        [hist_off[k]:hist_off[k + 1]] are the members that the replica set of k (n members, as route_n lists them)
+        holds under at least one counted observer row of this handle, ascending, and the number of counted rows whose
+        set holds each. The rows agree on key k exactly when every count equals counted
+        (swimsim.metrics.replica_agreement). who as for census()."""
+        n = _replica_n(n, "replica_census")
+        w = _census_who(who, "replica_census")
+        blob, off = _pack_keys(keys)
+        K = len(off) - 1
+        cap = max(1, 2 * n * K)
+        while True:
+            hoff = np.zeros(K + 1, np.uint64)
+            mem = np.empty(cap, np.int32)
+            cnt = np.empty(cap, np.uint32)
+            counted, nh, ms = C.c_uint32(), C.c_size_t(), C.c_double()
+            self._chk(load_library().swimsim_replica_census(self.h, blob, off.ctypes.data, K, int(replica_points), n, w,
+                                                            int(mode), C.byref(counted), hoff.ctypes.data,
+                                                            mem.ctypes.data, cnt.ctypes.data, cap, C.byref(nh),
+                                                            C.byref(ms)))
+            if nh.value <= cap:
+                return counted.value, hoff, mem[:nh.value].copy(), cnt[:nh.value].copy(), ms.value
+            cap = nh.value
+
     def address(self, m):
         """member m's address (the synthetic one unless the cluster was given addresses)"""
         a = getattr(self, "_addresses", None)
@@ -943,6 +997,25 @@ class ShardedCluster:
     def route_census(self, keys, who="live", replica_points=100, mode=0):
         return merge_route_histograms([c.route_census(keys, who, replica_points, mode) for c in self.shards])
 
+    def route_n(self, keys, observers, n=3, replica_points=100, mode=0):
+        n = _replica_n(n, "route_n")
+        obs = _member_list(observers)
+        if len(obs) and obs.max() >= self.n:
+            raise SwimsimError("EINVAL: route_n: observer out of range")
+        if not len(obs):
+            raise SwimsimError("EINVAL: route_n: no observers")
+        out = np.empty((len(obs), len(keys), n), np.int32)
+        srv = np.empty(len(obs), np.uint32)
+        for c in self.shards:
+            sel = np.nonzero((obs >= c.lo) & (obs < c.lo + c.nl))[0]
+            if len(sel):
+                out[sel], srv[sel] = c.route_n(keys, obs[sel], n, replica_points, mode)
+        return out, srv
+
+    def replica_census(self, keys, n=3, who="live", replica_points=100, mode=0):
+        n = _replica_n(n, "replica_census")
+        return merge_route_histograms([c.replica_census(keys, n, who, replica_points, mode) for c in self.shards])
+
     def address(self, m):
         return self.shards[0].address(m)
 
@@ -1145,3 +1218,8 @@ class Node:
         """(address, ok): the member this node sends `key` to; ok is False when its ring is empty"""
         m = int(self.c.route([key], [self.o], replica_points)[0, 0])
         return (self.c.address(m), True) if m >= 0 else ("", False)
+
+    def LookupN(self, key, n, replica_points=100):        # ringpop.go:611 over this node's own ring view
+        """the addresses of the (up to) n members this node holds responsible for `key`, in ring-walk order"""
+        prefs, _ = self.c.route_n([key], [self.o], n, replica_points)
+        return [self.c.address(int(m)) for m in prefs[0, 0] if m >= 0]

@@ -1,5 +1,5 @@
 """Failure-detection metrics from a member trace (Cluster.trace / ShardedCluster.trace) and routing agreement from
-a route census (Cluster.route_census / ShardedCluster.route_census).
+a route census (Cluster.route_census / ShardedCluster.route_census) or a replica census (replica_census).
 
 Plain numpy on the trace arrays: no device, no library. The status columns of a census count are alive, suspect,
 faulty, leave, tombstone, unknown (swimsim.CENSUS_STATUSES).
@@ -82,3 +82,35 @@ def route_agreement(counted, hist_off, hist_owner, hist_count) -> RouteAgreement
             j = a + int(np.argmax(hist_count[a:b]))                  # (argmax takes the first: the lowest owner)
             owner[k], count[k] = hist_owner[j], hist_count[j]
     return RouteAgreement(distinct, owner, count)
+
+
+@dataclass
+class ReplicaAgreement:
+    """per key of a replica census with sets of n members:
+    distinct:   the number of distinct members over the counted rows' replica sets;
+    unanimous:  the number of members every counted row lists (count = counted);
+    agreed:     every counted row holds the same replica set (every listed member is unanimous; true for a key
+                with no entry: no row counted, or every counted view empty)."""
+    distinct: np.ndarray
+    unanimous: np.ndarray
+    agreed: np.ndarray
+
+
+def replica_agreement(counted, hist_off, hist_member, hist_count, n) -> ReplicaAgreement:
+    """counted, hist_off[K + 1], hist_member, hist_count as replica_census(keys, n) returns them."""
+    hist_off = np.asarray(hist_off, dtype=np.int64).reshape(-1)
+    hist_member = np.asarray(hist_member, dtype=np.int64).reshape(-1)
+    hist_count = np.asarray(hist_count, dtype=np.int64).reshape(-1)
+    if len(hist_off) < 1 or len(hist_member) != len(hist_count) or hist_off[-1] != len(hist_member):
+        raise ValueError("replica_agreement: hist_off[K + 1] and hist_member / hist_count of hist_off[K] entries expected")
+    if not 1 <= int(n) <= 16:
+        raise ValueError(f"replica_agreement: n is 1..16, not {n!r}")
+    if len(hist_count) and (hist_count.min() < 1 or hist_count.max() > int(counted)):
+        raise ValueError("replica_agreement: every count is 1..counted")
+    K = len(hist_off) - 1
+    distinct = np.diff(hist_off)
+    full = np.concatenate([[0], np.cumsum(hist_count == int(counted))])
+    unanimous = full[hist_off[1:]] - full[hist_off[:-1]]
+    if (unanimous > int(n)).any():
+        raise ValueError(f"replica_agreement: a key lists more than n = {n} members in every counted row")
+    return ReplicaAgreement(distinct, unanimous, unanimous == distinct)
