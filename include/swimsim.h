@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define SWIMSIM_ABI_VERSION 10
+#define SWIMSIM_ABI_VERSION 11
 
 enum {
     SWIMSIM_OK = 0,
@@ -107,10 +107,20 @@ typedef struct swimsim_tuning {
                                  collides, the last store wins, the losing decisions fall through). Results are
                                  identical with every combination; <= 0 (default, and the 0 an older caller's
                                  zero-initialised struct reads): the production engine */
+    int32_t cs_defer;         /* lazy phase C (ABI 11): may a round inside a multi-round swimsim_step leave
+                                 its dirty rows unhashed for a later round of the same call? -1 or 1 (default): yes, when
+                                 a round follows in the call, the launch would stay on the main stream (more dirty rows
+                                 than cs_async_rows), at least 3/4 of the dirty rows changed in this round and the
+                                 round deferred at most NL/64 full-sync decisions; 0 (also what an older caller's
+                                 zero-initialised struct reads): every round hashes its dirty rows, as before ABI 11;
+                                 2 = tests only: whenever a round follows in the call. Every read-back and every
+                                 decision that needs a checksum still gets it; results are identical in every mode */
 } swimsim_tuning;
 /* Environment, read at swimsim_create (A/B experiments; results are identical either way): SWIMSIM_SYNC_SPIN=0 waits for
  * the main stream's host round trips in the runtime's stream wait instead of polling an event; SWIMSIM_SIDE2=0 runs both
- * generations of side-stream checksum launches on one stream. */
+ * generations of side-stream checksum launches on one stream; SWIMSIM_CS_DEFER=0|1|2 overrides
+ * swimsim_tuning.cs_defer; SWIMSIM_CS_DEFER_LOG=1 writes one stderr line per phase C that had a round to leave its rows
+ * to (round, dirty rows, rows written in the round, deferred decisions, carried or hashed). */
 
 /* Events applied in phase E of a round (docs/ROUND_SEMANTICS.md §4). */
 enum {
@@ -428,7 +438,10 @@ int swimsim_kernel_times(swimsim_t *h, const char **names, double *avg_ms, uint6
 int swimsim_enable_timing(swimsim_t *h, int32_t enable);
 /* the unit counts behind those byte figures since swimsim_enable_timing (rows hashed by each checksum kernel,
  * changes processed / applied by each merge kernel, records issued, ...): names[i], values[i]; "hot_slots" is
- * the number of hot-column slots in use now (not a count since the reset) */
+ * the number of hot-column slots in use now (not a count since the reset). The last three (ABI 11, lazy phase C,
+ * swimsim_tuning.cs_defer): "cs_skipped_rounds" = rounds whose phase C hashed nothing, "cs_carried_rows" = the dirty rows
+ * they left, summed over those rounds, "cs_forced" = rounds that would have skipped but deferred too many full-sync
+ * decisions and hashed */
 int swimsim_kernel_units(swimsim_t *h, const char **names, double *values, size_t cap, size_t *n);
 /* profiler window marker: one tiny kernel (k_profile_mark) on the engine's stream, after the side stream drained */
 int swimsim_profile_mark(swimsim_t *h, uint32_t id);

@@ -186,6 +186,10 @@ constexpr uint32_t ULOG_CAP = 1024, ULOG_STRIDE = ULOG_CAP + 256;
 // dirty at issue and not copied (the row is rebuilt on demand), SRC_CLAIM = being rebuilt at resolution time
 // (k_lazy_mat). Both stay below bit 31, which marks a remote sender's slot in a deferred decision.
 constexpr uint32_t SRC_PEND = 0x7FFFFFFEu, SRC_CLAIM = 0x7FFFFFFDu;
+// DS::dirty[ol]: 0 = cs[ol] (or the side slot cpslot[ol]) is the row's checksum; 1 = written since the last phase C
+// (every writer stores 1); DIRTY_CARRIED = dirty, left unhashed by a phase C and not written since (lazy phase C,
+// DESIGN.md §5). Readers test against 0; only k_list tells the two apart.
+constexpr uint32_t DIRTY_CARRIED = 2u;
 
 // hot slot of member m, SRC_NONE when m has none (or hot columns are off)
 __device__ __forceinline__ uint32_t hot_slot(const DS &d, uint32_t m) { return d.hidx ? d.hidx[m] : SRC_NONE; }

@@ -435,7 +435,14 @@ struct swimsim {
     uint32_t csr_side_min = 4097;                 // side launches of at least this many rows take the path (csr2)
     int fault_inject = 0;                         // swimsim_tuning.fault_inject (tests)
     int defer_test = 0;                           // swimsim_tuning.defer_test (tests)
-    bool colx_stale = false;                      // raw row writes marked every column: rebuilt at the next step
+    // lazy phase C: a round inside a multi-round step call may leave its dirty rows unhashed
+    int cs_defer = 1;                             // swimsim_tuning.cs_defer: 0 never, 1 the policy, 2 whenever a round follows
+    uint32_t rounds_left = 0;                     // rounds of the running step call after the current one
+    uint32_t round_deferred = 0;                  // full-sync decisions the current round's phases D and Q2 deferred
+    bool cs_carried = false;                      // some row is dirty because a phase C skipped it
+    bool cs_defer_log = false;                    // SWIMSIM_CS_DEFER_LOG=1: one stderr line per phase C that could skip
+    uint64_t cs_skipped_rounds = 0, cs_carried_rows = 0, cs_forced = 0, cs_units_base[3] = {0, 0, 0};
+    bool colx_stale = false;                     // raw row writes marked every column: rebuilt at the next step
 #ifdef SWIMSIM_DIAG
     // reference-row checksum path (swimsim_checksum_delta.hip), allocated at its first launch
     int csd_mode = 0;                             // SWIMSIM_CS_DELTA: 0 off, 1 wide launches, 2 every launch >= 1024 rows
@@ -1192,6 +1199,13 @@ int sync_side(swimsim *h) {
     return 0;
 }
 
+// lazy phase C's policy (swimsim_tuning.cs_defer 1). Fixed by reasoning, not fitted: "still changing" is a clear
+// majority, 3/4, of the dirty rows written in this round (in a wave every row is; once a wave has passed, only the
+// rows the last stragglers reach are, a few per cent); "few decisions" is NL/64: a deferred decision of a dirty
+// receiver copies its row (4 N bytes), so the copies made because rows were left unhashed stay below 1/64 of the rows,
+// under 2 % of the one pass over them that the skipped hash would have been.
+constexpr uint32_t CS_DEFER_CHANGED_NUM = 3, CS_DEFER_CHANGED_DEN = 4, CS_DEFER_MAX_DEFERRED_DIV = 64;
+
 int checksum_dirty(swimsim *h, int mode, bool async = false) {
     // phase C (async) reuses side half side_gen only: the other half's launch, from the round before, may still run
     const uint32_t g = h->side_gen;
@@ -1200,7 +1214,7 @@ int checksum_dirty(swimsim *h, int mode, bool async = false) {
     } else if (int rc = sync_side(h)) {
         return rc;
     }
-    HIPCHK(h, hipMemsetAsync(h->cnt, 0, 4, h->s));
+    HIPCHK(h, hipMemsetAsync(h->cnt, 0, 8, h->s));
     {
         Scope sc(h, F_CSPREP);
         hipLaunchKernelGGL(k_list, dim3(blocks_for_threads(h->NL)), dim3(256), 0, h->s, h->d, mode, h->tgt, h->failed,
@@ -1208,9 +1222,36 @@ int checksum_dirty(swimsim *h, int mode, bool async = false) {
     }
     if (mode != 0) return hash_rows(h, h->list, h->cnt, h->NL, ~0u);
     uint32_t *hn = h->hinfo + 8;
-    HIPCHK(h, hipMemcpyAsync(hn, h->cnt, 4, hipMemcpyDeviceToHost, h->s));
+    HIPCHK(h, hipMemcpyAsync(hn, h->cnt, 8, hipMemcpyDeviceToHost, h->s));   // dirty rows, and those written this round
     HIPCHK(h, stream_sync(h));
     const uint32_t n = *hn;
+    // lazy phase C: a wave of changes writes nearly every row in every round, so a checksum computed
+    // now is overwritten by the next round's, and nothing reads it in between but deferred full-sync decisions, which
+    // settle a dirty row without its checksum (pending-live senders, k_defer_eq, k_lazy_mat). Such a round leaves
+    // its dirty rows dirty for a later round of the same step call (the last round of a call never does, and every
+    // read-back lists the dirty rows again). Only when the launch would stay on the main stream (side-stream launches
+    // are off the critical path already), when the rows are still changing (a settled set is hashed, so quiet rounds
+    // have clean senders and known checksums), and when the round deferred few decisions (each deferred decision of
+    // a dirty receiver copies its row: a workload of empty-list pings must not pay that against unhashed rows).
+    if (async && h->cs_defer && h->rounds_left && n) {
+        const uint32_t changed = hn[1];
+        const bool wide = n > (h->cs_async ? h->snap_cap : 0u);
+        const bool moving = (uint64_t)changed * CS_DEFER_CHANGED_DEN >= (uint64_t)n * CS_DEFER_CHANGED_NUM;
+        const bool calm = h->round_deferred <= h->NL / CS_DEFER_MAX_DEFERRED_DIV;
+        const bool skip = h->cs_defer == 2 || (wide && moving && calm);
+        if (h->cs_defer_log)
+            fprintf(stderr, "cs_defer round %u: dirty %u changed %u deferred %u: %s\n", h->round, n, changed,
+                    h->round_deferred, skip ? "carried" : wide && moving ? "hashed (valve)" : "hashed");
+        if (skip) {
+            hipLaunchKernelGGL(k_carry, dim3(blocks_for_threads(h->NL)), dim3(256), 0, h->s, h->d);
+            h->cs_carried = true;
+            h->cs_skipped_rounds++;
+            h->cs_carried_rows += n;
+            return 0;
+        }
+        if (wide && moving) h->cs_forced++;
+    }
+    h->cs_carried = false;                                         // (every dirty row is hashed below)
     // async: snapshot the rows to hash, mark every dirty row clean (cpslot = the slot carrying its
     // checksum) and hash the snapshots on the side stream; the round reads cs[] only after sync_side
     auto go_side = [&](const uint32_t *rows, uint32_t n2, const uint32_t *vals, const uint32_t *dups) -> int {
@@ -1332,7 +1373,9 @@ int resolve_deferred(swimsim *h, int phase, MsgDesc *rdesc, uint32_t maxn) {
         uint32_t *hc = h->hinfo + 10;
         HIPCHK(h, hipMemcpyAsync(hc, h->cnt, 4, hipMemcpyDeviceToHost, h->s));
         HIPCHK(h, hipMemcpyAsync(hc + 1, h->cnt + 1, 4, hipMemcpyDeviceToHost, h->s));
+        HIPCHK(h, hipMemcpyAsync(h->hinfo + 14, h->defer_cnt, 4, hipMemcpyDeviceToHost, h->s));
         HIPCHK(h, stream_sync(h));
+        if (phase != 2) h->round_deferred += h->hinfo[14];         // (lazy phase C's valve, checksum_dirty)
         // the list holds main-stream snapshot slots only (k_defer_ids), so their hash needs nothing from the side
         // stream and runs beside the previous phase C's side-stream launch (both are latency-bound launches of
         // few rows); k_recv_finish then compares with side-stream checksums, so it waits for the side stream
@@ -1559,9 +1602,12 @@ int do_heal(swimsim *h, uint32_t o, std::vector<int32_t> *ret) {
 
 // one protocol round (docs/ROUND_SEMANTICS.md §4). With G > 1 shards every call is collective: the
 // exchanges sit at the same points on every shard.
-int step_one(swimsim *h, const swimsim_event *ev, size_t nev) {
+// rounds_left: rounds of the same swimsim_step call after this one (phase C may leave dirty rows to them)
+int step_one(swimsim *h, const swimsim_event *ev, size_t nev, uint32_t rounds_left) {
     const uint32_t r = h->round;
     const bool sharded = h->G > 1;
+    h->rounds_left = rounds_left;
+    h->round_deferred = 0;
     {
         hipEvent_t e = take_event(h);
         HIPCHK(h, hipEventRecord(e, h->s));
@@ -1948,6 +1994,13 @@ int swimsim_create(const swimsim_config *cfg, swimsim_t **out) {
     if (tun && tun->cs_ref >= 0) h->csr_mode = tun->cs_ref;
     if (tun && tun->fault_inject > 0) h->fault_inject = tun->fault_inject;
     if (tun && tun->defer_test > 0) h->defer_test = tun->defer_test;
+    if (tun && tun->cs_defer >= 0) h->cs_defer = tun->cs_defer;
+    if (const char *v = getenv("SWIMSIM_CS_DEFER")) h->cs_defer = atoi(v);   // (experiment: 0 = every round hashes)
+    if (const char *v = getenv("SWIMSIM_CS_DEFER_LOG")) h->cs_defer_log = atoi(v) != 0;
+    if (h->cs_defer < 0 || h->cs_defer > 2) {
+        h->err = "swimsim_tuning.cs_defer is -1, 0, 1 or 2";
+        return bail(SWIMSIM_EINVAL);
+    }
     if (h->fault_inject & 32) h->csr_ecap = 24;      // (tests: rows whose exception entries end within CSR_EREG of the cap)
     if (h->fault_inject & 256) h->csr_side_min = 1024;   // (tests: side launches of 1,024 rows and more take the path)
     if (const char *v = getenv("SWIMSIM_SYNC_SPIN")) h->sync_spin = atoi(v) != 0;   // (experiment: 0 = the runtime's wait)
@@ -2391,8 +2444,12 @@ int swimsim_step(swimsim_t *h, uint32_t nrounds, const swimsim_event *events, si
     for (uint32_t i = 0; i < nrounds; i++) {
         // (a refute or Reincarnate of this round writes incarnation round + k_o at most)
         if (int rc = ensure_ecap(h, h->round + (uint32_t)std::max(h->coff_max, ev_kmax) + 1)) return rc;
-        if (int rc = step_one(h, events, nevents)) return rc;
+        if (int rc = step_one(h, events, nevents, nrounds - 1 - i)) return rc;
     }
+    h->rounds_left = 0;
+    // (the last round's phase C never skips, so no row is carried here; kept for a call that ends another way)
+    if (h->cs_carried)
+        if (int rc = checksum_dirty(h, 0)) return rc;
     if (int rc = sync_side(h)) return rc;    // a step call returns with every checksum current
     if (!h->round_ev.empty()) {
         hipEvent_t e = take_event(h);
@@ -3686,6 +3743,9 @@ int swimsim_enable_timing(swimsim_t *h, int32_t enable) {
     uint64_t c[CTR_STRIDE];
     if (int rc = read_counters(h, c)) return rc;
     for (int i = 0; i < CTR_STRIDE; i++) h->fam_bytes_base[i] = c[i];
+    h->cs_units_base[0] = h->cs_skipped_rounds;
+    h->cs_units_base[1] = h->cs_carried_rows;
+    h->cs_units_base[2] = h->cs_forced;
     return SWIMSIM_OK;
 }
 
@@ -3747,13 +3807,16 @@ int swimsim_kernel_units(swimsim_t *h, const char **names, double *values, size_
                                "hot_slots", "diag_stamp4", "diag_stamp5", "diag_stamp6", "diag_stamp7",
                                "dense_resp", "dense_jobs", "jobs_applied", "dense_heal", "defer", "defer_eq", "defer_norow",
                                "defer_rep", "defer_undo", "defer_rep_diff", "defer_undo_diff", "defer_fs",
-                               "defer_undo_over", "defer_clean", "issue_snaps", "lazy_late", "lazy_mat"};
+                               "defer_undo_over", "defer_clean", "issue_snaps", "lazy_late", "lazy_mat",
+                               "cs_skipped_rounds", "cs_carried_rows", "cs_forced"};
     const int ki[] = {C_X_CS_ROWS, C_X_CS_ROWS_N, C_X_CS_DUP, C_X_MERGED, C_X_APPLIED, C_X_RISSUED, C_X_RCALLS,
                       C_X_MERGED_R, C_X_APPLIED_R, C_X_BUMPED, C_X_ISSUED, -1, C_NALL, C_NALL + 1, C_NALL + 2, C_NALL + 3,
                       -2, C_NALL + 4, C_NALL + 5, C_NALL + 6, C_NALL + 7, C_X_DENSE_RESP, C_X_DENSE_JOBS, C_X_JOBS_APPLIED,
                       C_X_DENSE_HEAL, C_X_DEFER, C_X_DEFER_EQ, C_X_DEFER_NOROW, C_X_DEFER_REP, C_X_DEFER_UNDO,
                       C_X_DEFER_REP_DIFF, C_X_DEFER_UNDO_DIFF, C_X_DEFER_FS, C_X_DEFER_UNDO_OVER, C_X_DEFER_CLEAN,
-                      C_X_ISSUE_SNAPS, C_X_LAZY_LATE, C_X_LAZY_MAT};
+                      C_X_ISSUE_SNAPS, C_X_LAZY_LATE, C_X_LAZY_MAT, -3, -4, -5};   // (-3..-5: lazy phase C, host counts)
+    const uint64_t lazy_c[3] = {h->cs_skipped_rounds - h->cs_units_base[0], h->cs_carried_rows - h->cs_units_base[1],
+                                h->cs_forced - h->cs_units_base[2]};
     static_assert(sizeof(kn) / sizeof(kn[0]) == sizeof(ki) / sizeof(ki[0]), "one counter per name");
     uint32_t hot = 0;                                              // hot slots in use now (not a delta)
     if (h->d.hot_cnt) {
@@ -3764,7 +3827,8 @@ int swimsim_kernel_units(swimsim_t *h, const char **names, double *values, size_
     for (size_t i = 0; i < k && i < cap; i++) {
         if (names) names[i] = kn[i];
         if (values)
-            values[i] = ki[i] == -1 ? (double)h->d.NBIT : ki[i] == -2 ? (double)hot : (double)(c[ki[i]] - h->fam_bytes_base[ki[i]]);
+            values[i] = ki[i] == -1 ? (double)h->d.NBIT : ki[i] == -2 ? (double)hot : ki[i] <= -3 ? (double)lazy_c[-3 - ki[i]]
+                                                                                : (double)(c[ki[i]] - h->fam_bytes_base[ki[i]]);
     }
     if (n) *n = k;
     return SWIMSIM_OK;

@@ -1289,13 +1289,28 @@ __global__ void k_select_exhaust(DS d, const uint32_t *exh_list, const uint32_t 
 __global__ void k_list(DS d, int mode, const int32_t *tgt, const uint8_t *failed, uint32_t *list, uint32_t *cnt) {
     const uint32_t ol = blockIdx.x * blockDim.x + threadIdx.x;
     if (ol >= d.NL) return;
-    bool take = d.dirty[ol] != 0;
+    const uint32_t dv = d.dirty[ol];
+    bool take = dv != 0;
     if (mode == 1) take = take && tgt[ol] >= 0;
     if (mode == 2) take = take && failed[ol];
     if (take) list[atomicAdd(cnt, 1u)] = ol;
     // (phase C: a listed row gets a new checksum, on the main stream or in a new side slot; a pending one of an older
-    // side half must not overwrite it when that half retires)
+    // side half must not overwrite it when that half retires. A phase C that then leaves the row dirty, k_carry, keeps
+    // it cleared: the row's next checksum is that of a later listing)
     if (take && mode == 0) d.cpslot[ol] = SRC_NONE;
+    // phase C also counts, in cnt[1], the dirty rows written since the last phase C: every writer stores 1, a phase C
+    // that carries a row stores DIRTY_CARRIED (one add per wave)
+    if (mode == 0) {
+        const unsigned long long fresh = __ballot(dv == 1u);
+        if (fresh && lane_id() == 0) atomicAdd(cnt + 1, (uint32_t)__popcll(fresh));
+    }
+}
+
+// lazy phase C: the dirty rows stay dirty ("carried") for a later round of the same step call; every reader of
+// DS::dirty tests it against 0, so a carried row is a dirty row everywhere else
+__global__ void k_carry(DS d) {
+    const uint32_t ol = blockIdx.x * blockDim.x + threadIdx.x;
+    if (ol < d.NL && d.dirty[ol]) d.dirty[ol] = DIRTY_CARRIED;
 }
 
 __global__ void k_list_one(uint32_t *list, uint32_t *cnt, uint32_t ol, const DS d) {
