@@ -28,7 +28,8 @@
 extern "C" {
 #endif
 
-#define SWIMSIM_ABI_VERSION 11
+#define SWIMSIM_ABI_VERSION 12   /* 12: the checksum block-stream dump call is gone (only a diagnostics build ever
+                                    implemented it, and that build is gone); nothing else changed since 11 */
 
 enum {
     SWIMSIM_OK = 0,
@@ -449,8 +450,8 @@ int swimsim_profile_mark(swimsim_t *h, uint32_t id);
  * nrows rows, 1: the wide kernel (k_checksum3), 2: the narrow kernel (k_checksum_q16), 4: k_checksum3 with four row
  * groups per workgroup, 5: the reference-row path forced (reference row, k_csd_scan, k_csr_rec, k_csr3 and the
  * fallback launches for the rows it leaves), 6: the same on the side stream with its own buffer set (csr2; at most
- * 12,288 rows; SWIMSIM_EINVAL when the set was not allocated); other modes (diagnostic variants) only in the diagnostics library
- * tools/libswimsim_diag.so */
+ * 12,288 rows; SWIMSIM_EINVAL when the set was not allocated). Every other mode is SWIMSIM_EINVAL (up to ABI 11 a
+ * diagnostics build, since removed, took more) */
 int swimsim_bench_checksum(swimsim_t *h, uint32_t nrows, int32_t mode, int32_t reps, double *ms);
 /* the reference-row checksum path so far (swimsim_checksum_ref.hip + swimsim_checksum_csr.hip; swimsim_tuning.cs_ref =
  * 0 off, 1 wide launches, 2 every launch of >= 1024 rows): its launches, the rows it left to the production kernels
@@ -458,8 +459,6 @@ int swimsim_bench_checksum(swimsim_t *h, uint32_t nrows, int32_t mode, int32_t r
  * exception slots of a wave, 5..7 reserved = 0), how many of those rows had it. The counts are kept on the device and
  * read here (no host synchronisation inside a round). */
 int swimsim_checksum_path_stats(swimsim_t *h, uint64_t *delta_launches, uint64_t *fallback_rows, uint64_t *reasons);
-/* diagnostics library only: the 32-bit words of every 20-byte block the checksum kernel hashes for row o (W = 19) */
-int swimsim_debug_cs_stream(swimsim_t *h, uint32_t o, uint32_t *out, size_t cap_words);
 
 /* ---- shards: one cluster's observer rows split over G shards ----
  * The reference runs one swim.Node per process; here a shard owns observer rows

@@ -9,9 +9,9 @@
 //                  formatter wave and a hasher wave;
 //   k_checksum_q16 (swimsim_checksum4.hip): launches of at most CS_NARROW_ROWS rows (latency-bound), 16 rows per
 //                  workgroup, the chain in carried-sum form on lane quads fed by premix and formatter waves.
-// Superseded kernels (the 4-wave k_checksum, k_checksum_n16, k_checksum2) and every diagnostic variant live in
-// tools/diag/swimsim_checksum_diag.hip and are compiled only into the diagnostics library
-// (make -C ringpop-go_amd diag -> tools/libswimsim_diag.so), never into libswimsim.so.
+// Launches of many nearly equal rows go by a shared reference row first (swimsim_checksum_ref.hip,
+// swimsim_checksum_csr.hip); the two kernels above hash what that path leaves. Superseded kernels (the 4-wave
+// k_checksum, k_checksum_n16, k_checksum2) are in git history only.
 // The string length and the last included member (the FarmHash-mk prologue hashes the last 20
 // bytes before the chain) come from per-row values kept current by the merges.
 
@@ -144,12 +144,6 @@ constexpr int cs_no(int W, int maxtail) { return (3 + W + maxtail + 3) / 4; }
 #include "swimsim_checksum4.hip"
 #include "swimsim_checksum_ref.hip"
 #include "swimsim_checksum_csr.hip"
-#ifdef SWIMSIM_DIAG                            // tools/diag (diagnostics library only): the reference-row path
-#include "swimsim_checksum_delta.hip"          // (off by default in round 3, not a win over the cascade), the 3-wave
-#include "swimsim_checksum5.hip"               // and fast-path experiments and every superseded kernel
-#include "swimsim_checksum6.hip"
-#include "swimsim_checksum_diag.hip"
-#endif
 
 // up to CS_NARROW_ROWS rows (measured crossover) the launch is latency-bound: k_checksum_q16 (16 rows per
 // workgroup; 16 records per step up to 4,096 rows, 8 above); above, the 64-row throughput kernel k_checksum3

@@ -7,7 +7,7 @@
 //   wave 1 (H): runs all three FarmHash-mk lanes of every row (h, and the coupled g and f) over the blocks F
 //               completed one step earlier, the M() premixes included.
 // Included by swimsim_checksum.hip (record tables, buffer geometry C2_* and lds_barrier are defined there). The
-// superseded k_checksum2, whose formatter wave also ran the h lane, lives in tools/diag.
+// superseded k_checksum2, whose formatter wave also ran the h lane, is in git history only.
 //
 // Why the split moved: the chain arithmetic needs no LDS round trip of its own, while the formatter's work is
 // LDS-latency bound (carry copy, record writes, address-word broadcasts). With the h lane on the formatter,

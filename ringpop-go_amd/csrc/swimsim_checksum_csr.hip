@@ -26,19 +26,13 @@ constexpr int CSR_ROWS = 256;          // rows per workgroup (4 row groups of 64
 constexpr int CSR_SB = 32;             // blocks per super step
 constexpr int CSR_WINMAX = 1024;       // window entries per buffer: phases in use x Wn
 constexpr int C3_NB = 3;               // k_csr3's window and code table buffers (super step t: buffer t % 3)
-#ifndef C3_CTR_AT_DEF
-#define C3_CTR_AT_DEF 26
-#endif
 // the chain block at which a chain wave reads the next super step's hand-over counters (26: 4.66 / 7.41 ms on real
 // cascade rounds 14 / 18 at 65,536 rows, against 4.79 / 7.45 read before block 0 and 4.62 / 7.44 at block 16; a read
 // that comes too early finds the stagers short and costs a wait of an LDS round trip)
-constexpr int C3_CTR_AT = C3_CTR_AT_DEF;
+constexpr int C3_CTR_AT = 26;
 constexpr uint32_t CSR_ESZ = 16;       // a code's unit: an entry's byte offset in each of the two entry arrays
 constexpr int CSR_EREG = 4;            // exception entries of a record prefetched with it
-#ifndef CSR_PF_DEF
-#define CSR_PF_DEF 6
-#endif
-constexpr int CSR_PF = CSR_PF_DEF;     // blocks the chain's LDS reads run ahead of its arithmetic (6: 7.37 / 11.52 ms
+constexpr int CSR_PF = 6;              // blocks the chain's LDS reads run ahead of its arithmetic (6: 7.37 / 11.52 ms
                                        // on rounds 14 / 18 against 7.48 / 11.69 with 4 and 8.00 / 12.00 with 2)
 constexpr uint32_t CSR_F_PLAN = 128, CSR_F_SLOTS = 256, CSR_F_RCAP = 512;   // flags beyond k_csd_scan's
 
@@ -245,7 +239,7 @@ __global__ void __launch_bounds__(256) k_csr_rec(DS d, const uint32_t *list, uin
 // ---------------------------------------------------------------------------------------------------------------
 // k_csr3: chain waves that only run chains (round 5). k_csr2's waves spent 39 % (light rounds) to 55 % (heavy) of
 // their loop outside the chain: staging the next super step's window, unpacking records, writing exception entries,
-// and waiting at the per-super-step barrier for the slowest of the eight (shader-clock stamps, tools/csr_stamps.py).
+// and waiting at the per-super-step barrier for the slowest of the eight (shader-clock stamps).
 // Here two more waves per SIMD do all of that ahead of the chains, the record stager (lane = row: codes, exception
 // entries) and the window stager (a quarter of the window, three super steps ahead), and no barrier is left in the
 // loop. The window and the codes are triple-buffered (window buffer and code table t % 3) and the exception entries
@@ -293,12 +287,8 @@ __device__ __forceinline__ void c3_wait(const uint32_t *ctr, uint32_t target) {
 // both kinds of chain wave (g/f: ctr[0][i], h: ctr[1][i]) have reached target
 template <int NI>
 __device__ __forceinline__ void c3_wait2(const uint32_t (&ctr)[2][NI], uint32_t i, uint32_t target) {
-#ifdef C3_T_SHAREDDONE
-    c3_wait(&ctr[0][i], 2u * target);                                // (test build: round 5's racy shared count)
-#else
     c3_wait(&ctr[0][i], target);
     c3_wait(&ctr[1][i], target);
-#endif
 }
 __device__ __forceinline__ void c3_signal(uint32_t *ctr) {
     if ((threadIdx.x & 63u) == 0) __hip_atomic_fetch_add(ctr, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -343,9 +333,6 @@ __device__ __forceinline__ C3Row c3_row(const DS &d, const uint32_t *list, uint3
 __device__ __forceinline__ void c3_stage(const DS &d, const uint32_t *list, uint32_t cnt, const CsrArgs &a, const CsrPlan &p,
                                          Csr3Lds &L, uint32_t T_) {
     const uint32_t tid = threadIdx.x & (CSR_ROWS - 1), rwave = tid >> 6;
-#if defined(C3_SPRIO) && C3_SPRIO > 0
-    __builtin_amdgcn_s_setprio(C3_SPRIO);
-#endif
     if (a.stprio) __builtin_amdgcn_s_setprio(1);
     C3Row r = c3_row(d, list, cnt, a, p, tid);
     const CsrRec *rec = a.rec + (size_t)(r.valid ? r.gi : blockIdx.x * CSR_ROWS) * a.rcap;
@@ -386,27 +373,11 @@ __device__ __forceinline__ void c3_stage(const DS &d, const uint32_t *list, uint
         else return tg2;
     };
     // one super step's codes and exceptions of this row into code buffer k (window buffer b)
-#ifdef CSR_DIAG_NE
-    uint64_t dg_[4] = {0, 0, 0, 0};
-#endif
     auto prep = [&](uint32_t t, uint32_t b, auto KC) {
         constexpr uint32_t k = decltype(KC)::value;
-#ifdef C3_T_NOREC
-        const bool has = false;
-#else
         const bool has = r.live && rv && R0.x == t;
-#endif
         if (__ballot(has)) {
             uint32_t ne = has && !(r.fl & CSR_F_SLOTS) ? R0.w : 0u, tot = 0;
-#ifdef CSR_DIAG_NE
-            {                                                       // (diagnostics: record super steps, long ones)
-                const uint64_t bh = __ballot(has), bl = __ballot(ne > (uint32_t)CSR_EREG);
-                dg_[0]++;
-                dg_[1] += (uint64_t)__popcll(bh);
-                dg_[2] += bl ? 1u : 0u;
-                dg_[3] += (uint64_t)__popcll(bl);
-            }
-#endif
             const uint32_t sb = wscan_excl(ne, tot);
             // ring slots for the wave's exceptions; rows past the ring's size are left to the production kernels
             const bool over = has && ne > 0 && sb + ne > R;
@@ -478,47 +449,14 @@ __device__ __forceinline__ void c3_stage(const DS &d, const uint32_t *list, uint
         if (adv) { base = csr_base(p, s); rcur++; ecur += R0.w; }
         if (__ballot(adv)) load_rec(rcur, ecur);
     };
-#ifdef CSR_DIAG_STAMP
-    // (diagnostic build only: the stagers' shader-clock stamps into diagnostic counters 4-7: waiting for the chains,
-    // the window, the rows' codes and exceptions, the hand-over)
-    uint64_t st_[4] = {0, 0, 0, 0};
-    auto stamp = [&]() -> uint64_t {
-        uint64_t tt;
-        __builtin_amdgcn_sched_barrier(0);
-        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(tt) :: "memory");
-        __builtin_amdgcn_sched_barrier(0);
-        return tt;
-    };
-#define C3S_STAMP(v) const uint64_t v = stamp()
-#define C3S_ACC(k, x) st_[k] += (x)
-#else
-#define C3S_STAMP(v)
-#define C3S_ACC(k, x)
-#endif
     auto step = [&](uint32_t u, auto BC, auto KC) {
         constexpr uint32_t b = decltype(BC)::value;
-        C3S_STAMP(s0);
         c3_jitter(a.jitter, 2, u, 0);
         if (u >= 3) c3_wait2(L.doner, rwave, u - 2u);               // this group's chains are done with super step u - 3
-        C3S_STAMP(s1);
-#ifdef CSR_DIAG_STAMP
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");            // (diagnostics: slot 1 = the record loads' wait)
-#endif
-        C3S_STAMP(s2);
         prep(u, b, KC);
         e3 = e2; e2 = e1; e1 = alloc;
-        C3S_STAMP(s3);
         c3_jitter(a.jitter, 2, u, 1);
         c3_signal(&L.readyr[rwave]);
-        C3S_STAMP(s4);
-        C3S_ACC(0, s1 - s0);
-#ifndef CSR_DIAG_WINDOW
-        C3S_ACC(1, s2 - s1);
-#endif
-        C3S_ACC(2, s3 - s2);
-#ifndef CSR_DIAG_WINDOW
-        C3S_ACC(3, s4 - s3);
-#endif
     };
     using I0 = std::integral_constant<uint32_t, 0>;
     using I1 = std::integral_constant<uint32_t, 1>;
@@ -530,16 +468,6 @@ __device__ __forceinline__ void c3_stage(const DS &d, const uint32_t *list, uint
         if (u + 2 >= T_) break;
         step(u + 2, I2{}, I2{});
     }
-#ifdef CSR_DIAG_STAMP
-    if ((threadIdx.x & 63u) == 0)
-        for (int k = 0; k < 4; k++) ctr_add(d, C_NALL + 4 + k, (unsigned long long)st_[k]);
-#endif
-#undef C3S_STAMP
-#undef C3S_ACC
-#ifdef CSR_DIAG_NE
-    if ((threadIdx.x & 63u) == 0)
-        for (int k = 0; k < 4; k++) ctr_add(d, C_NALL + 4 + k, (unsigned long long)dg_[k]);
-#endif
     L.FLX[tid] = r.fl;
 }
 
@@ -548,9 +476,6 @@ __device__ __forceinline__ void c3_stage(const DS &d, const uint32_t *list, uint
 // stamps: in the record stager's loop the window took 34-43 % of the chain waves' loop, and the chains waited for it.
 __device__ __forceinline__ void c3_wstage(const CsrArgs &a, const CsrPlan &p, Csr3Lds &L, uint32_t T_) {
     const uint32_t tid = threadIdx.x & (CSR_ROWS - 1);
-#if defined(C3_WPRIO) && C3_WPRIO > 0
-    __builtin_amdgcn_s_setprio(C3_WPRIO);
-#endif
     if (a.stprio) __builtin_amdgcn_s_setprio(1);
     // window: entries u = tid + 256 v (both halves), two register sets (super step u -> set u & 1), loaded two ahead
     constexpr int WV = CSR_WINMAX / CSR_ROWS;
@@ -571,12 +496,8 @@ __device__ __forceinline__ void c3_wstage(const CsrArgs &a, const CsrPlan &p, Cs
         for (int v = 0; v < WV; v++) {
             const int32_t k = min(max(wk0[v] + (int32_t)(t * CSR_SB), 0), (int32_t)a.KP - 1);
             const uint4 *src = a.P + 2 * (size_t)(wsrc[v] + (uint32_t)k);
-#ifdef C3_T_NOWIN
-            w0[v] = u32x4{(uint32_t)k, 1u, 2u, 3u}; w1[v] = u32x2{(uint32_t)k, 5u}; (void)src;
-#else
             w0[v] = *(const u32x4 *)src;
             w1[v] = *(const u32x2 *)(src + 1);
-#endif
         }
     };
     auto wstore = [&](const u32x4 (&w0)[WV], const u32x2 (&w1)[WV], uint32_t b) {
@@ -626,42 +547,19 @@ __device__ __forceinline__ void c3_chain(const DS &d, const uint32_t *list, uint
     const bool ok = cs_prologue<W>(d, r.id, r.is_row, row, fh, it2);
     uint32_t X0 = GF ? fh.g + r.ri.b0 : fh.h + r.ri.a0;             // Xg, or Xh
     uint32_t X1 = GF ? fh.f + r.ri.c0 : 0u;                         // Xf
-#ifdef CSR_DIAG_STAMP
-    // (diagnostic build only: shader-clock stamps of the g/f waves, summed into the diagnostic counters: 0 chain,
-    // 1 waiting for the stagers, 2 codes, 3 whole loop)
-    uint64_t st_[4] = {0, 0, 0, 0};
-    auto stamp = [&]() -> uint64_t {
-        uint64_t tt;
-        __builtin_amdgcn_sched_barrier(0);
-        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(tt) :: "memory");
-        __builtin_amdgcn_sched_barrier(0);
-        return tt;
-    };
-#define C3_STAMP(v) const uint64_t v = stamp()
-#define C3_ACC(k, x) st_[k] += (x)
-#else
-#define C3_STAMP(v)
-#define C3_ACC(k, x)
-#endif
-    C3_STAMP(tl0);
     uint32_t code[CSR_SB];
     uint32_t pr = 0, pw = 0;                                         // the hand-over counters, as last read
     // super step t = 3 j + b: window and code buffer b
     auto step = [&](uint32_t t, uint32_t j, auto BC) {
         constexpr uint32_t b = decltype(BC)::value;
         const uint32_t K0 = t * CSR_SB;
-        C3_STAMP(ta);
         c3_jitter(a.jitter, ROLE, t, 0);
         // this group's record stager has staged super step t, and the window stagers its window: the counters were
         // read near the end of the last super step's chain (an LDS round trip per read, 10 % of a light round's loop
         // when read here); only when they were short is there a wait, then an acquire fence for what they hand over
         if (pr < t + 1u) c3_wait(&L.readyr[grp], t + 1u);
-#ifdef CSR_DIAG_SPLITWAIT
-        C3_STAMP(tw);                                               // (diagnostics: slot 2 = the window's wait)
-#endif
         if (pw < 4u * (j + 1u)) c3_wait(&L.readyw[b], 4u * (j + 1u));
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-        C3_STAMP(tb);
 #pragma unroll
         for (int q = 0; q < 4; q++) {
             const uint4 v = L.TC[b][q][tid];
@@ -672,7 +570,6 @@ __device__ __forceinline__ void c3_chain(const DS &d, const uint32_t *list, uint
                 else { code[8 * q + 2 * j] = __builtin_amdgcn_ubfe(w4[j], 1, 15); code[8 * q + 2 * j + 1] = w4[j] >> 17; }
             }
         }
-        C3_STAMP(tc);
         const bool full = __all(myit == 0u || K0 + CSR_SB <= myit);
         const char *Eb = GF ? (const char *)L.EA : (const char *)L.EB;
         auto run = [&](auto FULLC) {
@@ -705,24 +602,8 @@ __device__ __forceinline__ void c3_chain(const DS &d, const uint32_t *list, uint
         if (full) run(std::integral_constant<bool, true>{});
         else run(std::integral_constant<bool, false>{});
         c3_jitter(a.jitter, ROLE, t, 1);
-#ifdef C3_T_SHAREDDONE
-        c3_signal(&L.done[0][b]);
-        c3_signal(&L.doner[0][grp]);
-#else
         c3_signal(&L.done[ROLE][b]);
         c3_signal(&L.doner[ROLE][grp]);
-#endif
-        C3_STAMP(td);
-        C3_ACC(0, td - tc);
-#ifdef CSR_DIAG_SPLITWAIT
-        C3_ACC(1, tw - ta);
-        C3_ACC(2, tb - tw);
-#else
-        C3_ACC(1, tb - ta);
-#endif
-#if !defined(CSR_DIAG_WINDOW) && !defined(CSR_DIAG_SPLITWAIT)
-        C3_ACC(2, tc - tb);
-#endif
     };
     for (uint32_t t = 0, j = 0; t < T_; t += 3, j++) {
         step(t, j, std::integral_constant<uint32_t, 0>{});
@@ -731,14 +612,6 @@ __device__ __forceinline__ void c3_chain(const DS &d, const uint32_t *list, uint
         if (t + 2 >= T_) break;
         step(t + 2, j, std::integral_constant<uint32_t, 2>{});
     }
-    C3_STAMP(tl1);
-    C3_ACC(3, tl1 - tl0);
-#ifdef CSR_DIAG_STAMP
-    if (GF && (threadIdx.x & 63u) == 0)
-        for (int k = 0; k < 4; k++) ctr_add(d, C_NALL + k, (unsigned long long)st_[k]);
-#endif
-#undef C3_STAMP
-#undef C3_ACC
     if constexpr (!GF) L.XH[tid] = X0;
     out = make_uint3(X0, X1, ok ? 1u : 0u);
 }
@@ -788,16 +661,7 @@ __global__ void __launch_bounds__(4 * CSR_ROWS) k_csr3(DS d, const uint32_t *lis
     if (role == 0) c3_chain<W, 0>(d, list, cnt, a, p, L, T_, X);
     else if (role == 1) c3_chain<W, 1>(d, list, cnt, a, p, L, T_, X);
     else if (role == 2) c3_stage(d, list, cnt, a, p, L, T_);
-    else {
-        c3_wstage(a, p, L, T_);
-#if defined(CSR_DIAG_STAMP) && defined(CSR_DIAG_WINDOW)
-        if (threadIdx.x == 3 * CSR_ROWS) {                          // (diagnostics: window geometry per super step)
-            ctr_add(d, C_NALL + 2, (unsigned long long)T_);
-            ctr_add(d, C_NALL + 5, (unsigned long long)T_ * p.nph * p.Wn);
-            ctr_add(d, C_NALL + 7, (unsigned long long)T_ * p.nph);
-        }
-#endif
-    }
+    else c3_wstage(a, p, L, T_);
     __syncthreads();                                                // (every role: XH and the stagers' FLX)
     if (role == 0) c3_finish<W>(d, list, cnt, a, p, L, X);
 }

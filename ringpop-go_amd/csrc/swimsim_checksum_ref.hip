@@ -1,6 +1,5 @@
-// swimsim_checksum_ref.hip — the reference-row pieces of phase C (memberlist.go:83-128, go-farm Fingerprint32) shared by
-// the product's reference-row kernel (k_csr, swimsim_checksum_csr.hip) and the diagnostics library's k_cs_delta
-// (tools/diag/swimsim_checksum_delta.hip). Included by swimsim_checksum.hip.
+// swimsim_checksum_ref.hip — the reference-row pieces of phase C (memberlist.go:83-128, go-farm Fingerprint32) that the
+// reference-row kernel (k_csr3, swimsim_checksum_csr.hip) builds on. Included by swimsim_checksum.hip.
 //
 // The rows hashed in one round are views of the same membership: in a cascade round a row differs from the
 // column-wise majority of the rows in 0.1-100 of 65,536 members (tools/delta_probe.py, profiles/r03_delta_probe.json).
@@ -51,18 +50,7 @@ struct CsdArgs {
     const uint32_t *ucnt;     // their number
     const uint4 *ucol;        // per divergent column c: {m, B[m], O_B[m], O_B[m - 1]} (k_csr_ucol)
     const uint32_t *uhk;      // per divergent column c: the hot slot of its member, or SRC_NONE (DS::uhk)
-    uint32_t dmode;           // diagnostics library only (swimsim_bench_checksum modes 31..46 = dmode + 30, garbage
-                              // checksums): 1 helpers alone, 2 chains alone, 3 helpers without the exception work; bit 8:
-                              // no barrier between super steps. Ignored by the product library (CSD_DMODE)
 };
-
-// the diagnostic split modes exist only in the diagnostics library (tools/libswimsim_diag.so); in the product
-// library the mode is the constant 0 and its branches compile away
-#ifdef SWIMSIM_DIAG
-#define CSD_DMODE(a) ((a).dmode)
-#else
-#define CSD_DMODE(a) 0u
-#endif
 
 __device__ __forceinline__ const uint32_t *csd_row(const DS &d, uint32_t id) {
     return id < d.NL ? d.mw + (size_t)id * d.NP : d.dense + (size_t)(id - d.NL) * d.NP;
@@ -106,21 +94,6 @@ __global__ void k_csd_ref(DS d, const uint32_t *list, uint32_t n, uint32_t *B, u
     B[m] = cand;
     Lb[m] = csd_reclen(d, cand);
 }
-
-#ifdef SWIMSIM_DIAG
-// (diagnostics library only: round 3's path declines launches on a sample; the product's path never declines)
-// the launch's mean distance from B, on CSD_NSAMPLE rows sampled evenly from the list: differing members counted
-// into *out (one workgroup per sampled row). Decides whether the reference-row path pays for this launch.
-constexpr uint32_t CSD_NSAMPLE = 64;
-__global__ void __launch_bounds__(256) k_csd_sample(DS d, const uint32_t *list, uint32_t n, const uint32_t *B, uint32_t *out) {
-    const uint32_t id = list[(uint32_t)(((uint64_t)blockIdx.x * n) / CSD_NSAMPLE)];
-    const uint32_t *row = csd_row(d, id);
-    uint32_t c = 0;
-    for (uint32_t m = threadIdx.x; m < d.N; m += 256u) c += csd_same(row[m], B[m]) ? 0u : 1u;
-    for (int off = 32; off > 0; off >>= 1) c += (uint32_t)__shfl_xor((int)c, off, 64);
-    if ((threadIdx.x & 63u) == 0 && c) atomicAdd(out, c);
-}
-#endif
 
 // the divergent columns' scan table: what k_csd_scan needs of B at each, in one 16-B load
 __global__ void k_csr_ucol(const uint32_t *ulist, const uint32_t *ucnt, const uint32_t *B, const uint32_t *OB, uint4 *ucol) {
@@ -213,10 +186,7 @@ __device__ void csd_run_entries(const DS &d, const uint32_t *row, uint32_t m0, u
 template <int W>
 // (five workgroups per CU: 96 VGPRs, five waves per SIMD for a latency-bound gather; with 8 chunks in flight and four
 // waves per SIMD the path took 0.05-0.15 ms longer on real cascade rounds 14-20, with six it spilled)
-#ifndef CSD_SCAN_MINB
-#define CSD_SCAN_MINB 5
-#endif
-__global__ void __launch_bounds__(256, CSD_SCAN_MINB) k_csd_scan(DS d, const uint32_t *list, uint32_t n, CsdArgs a) {
+__global__ void __launch_bounds__(256, 5) k_csd_scan(DS d, const uint32_t *list, uint32_t n, CsdArgs a) {
     // CSD_SU chunks of 64 members per pass, their loads in flight together (a row is one 256-KB stream). A chunk's
     // differing members are taken together, one per lane: the shift before each is a wave prefix sum of the record
     // length differences, a member starts a new run of exception blocks when its first block lies past the previous
@@ -224,10 +194,7 @@ __global__ void __launch_bounds__(256, CSD_SCAN_MINB) k_csd_scan(DS d, const uin
     // before it (prefix sums place the closed runs and their entries). Round 4's first version walked the members one
     // at a time (the whole wave, scalar): 5.9 ms per launch on a heavy cascade round. Runs wait in LDS for their
     // entries, generated (one lane per run) between passes.
-#ifndef CSD_SU_DEF
-#define CSD_SU_DEF 4
-#endif
-    constexpr uint32_t CSD_SU = CSD_SU_DEF, RUNCAP = 256, RUNFLUSH = 128;
+    constexpr uint32_t CSD_SU = 4, RUNCAP = 256, RUNFLUSH = 128;
     __shared__ uint32_t runs[4][RUNCAP][6];                         // {klo, khi, m0, o0, s_after, first entry}
     const uint32_t wv = threadIdx.x >> 6, lane = threadIdx.x & 63u;
     const uint32_t i = blockIdx.x * 4 + wv;
@@ -430,12 +397,8 @@ __global__ void __launch_bounds__(256, CSD_SCAN_MINB) k_csd_scan(DS d, const uin
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// k_cs_delta: the chains
+// the chains' block steps (k_csr3)
 // ---------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t csd_alignbyte(uint32_t hi, uint32_t lo, uint32_t sh) {
-    return __builtin_amdgcn_alignbyte(hi, lo, sh);
-}
-
 // one block of the coupled g and f lanes in carried-sum form, the two lanes' instructions interleaved (a wave issues in
 // order: each of a pair's dependent successors then waits one instruction less)
 __device__ __forceinline__ void csd_gf_step(uint32_t &Xg, uint32_t &Xf, uint32_t mg, uint32_t dd, uint32_t mf, uint32_t pf) {
@@ -450,29 +413,6 @@ __device__ __forceinline__ void csd_gf_step(uint32_t &Xg, uint32_t &Xf, uint32_t
                  "v_add3_u32 %0, %2, %1, %5"
                  : "+v"(Xg), "+v"(Xf), "=&v"(tg), "=&v"(tf)
                  : "v"(mg), "v"(dd), "v"(mf), "v"(pf));
-}
-// one block of all three lanes as one sequence, the g, f and h instructions interleaved so that every instruction's
-// operands were produced at least two instructions earlier (also across consecutive blocks): a dependent integer VALU
-// instruction issues about 10 cycles after its producer, an independent one every 5, so the block runs at the issue
-// rate, 12 instructions. (csd_gf_step followed by csd_h_step leaves the four h instructions back to back: the compiler
-// does not interleave separate asm statements.)
-__device__ __forceinline__ void csd_block3(uint32_t &Xg, uint32_t &Xf, uint32_t &Xh, uint32_t mg, uint32_t dd, uint32_t mf,
-                                           uint32_t pf, uint32_t mh, uint32_t kh) {
-    uint32_t tg, tf;
-    asm volatile("v_xor_b32 %4, %1, %7\n\t"
-                 "v_xor_b32 %3, %0, %5\n\t"
-                 "v_xor_b32 %2, %2, %9\n\t"
-                 "v_alignbit_b32 %4, %4, %4, 19\n\t"
-                 "v_alignbit_b32 %3, %3, %3, 19\n\t"
-                 "v_alignbit_b32 %2, %2, %2, 19\n\t"
-                 "v_lshl_add_u32 %3, %3, 2, %3\n\t"
-                 "v_lshl_add_u32 %4, %4, 2, %4\n\t"
-                 "v_lshl_add_u32 %2, %2, 2, %2\n\t"
-                 "v_add3_u32 %1, %4, %3, %8\n\t"
-                 "v_add_u32 %2, %2, %10\n\t"
-                 "v_add3_u32 %0, %3, %1, %6"
-                 : "+v"(Xg), "+v"(Xf), "+v"(Xh), "=&v"(tg), "=&v"(tf)
-                 : "v"(mg), "v"(dd), "v"(mf), "v"(pf), "v"(mh), "v"(kh));
 }
 // one block of the h lane: Xh' = 5 ror(Xh ^ Mh, 19) + KH
 __device__ __forceinline__ void csd_h_step(uint32_t &Xh, uint32_t mh, uint32_t kh) {

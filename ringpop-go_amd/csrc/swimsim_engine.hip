@@ -443,23 +443,6 @@ struct swimsim {
     bool cs_defer_log = false;                    // SWIMSIM_CS_DEFER_LOG=1: one stderr line per phase C that could skip
     uint64_t cs_skipped_rounds = 0, cs_carried_rows = 0, cs_forced = 0, cs_units_base[3] = {0, 0, 0};
     bool colx_stale = false;                     // raw row writes marked every column: rebuilt at the next step
-#ifdef SWIMSIM_DIAG
-    // reference-row checksum path (swimsim_checksum_delta.hip), allocated at its first launch
-    int csd_mode = 0;                             // SWIMSIM_CS_DELTA: 0 off, 1 wide launches, 2 every launch >= 1024 rows
-    bool csd_ready = false, csd_failed = false;
-    uint32_t csd_rows = 0;                        // rows a launch may hold
-    uint32_t *csd_B = nullptr, *csd_Lb = nullptr, *csd_OB = nullptr, *csd_SBw = nullptr, *csd_fb = nullptr,
-             *csd_fbcnt = nullptr;
-    size_t csd_sbw_words = 0;
-    uint4 *csd_ent = nullptr;
-    CsdRow *csd_rinfo = nullptr;
-    uint32_t csd_ecap = 3072;
-    uint64_t csd_launches = 0, csd_fallback_rows = 0, csd_reasons[CSD_NFLAGS] = {0};
-    uint32_t csd_maxdiff = 12;                    // SWIMSIM_CS_DELTA_MAXDIFF: mean differing members per sampled row above
-                                                  // which a launch keeps the production kernels (0: always the path)
-    uint64_t csd_declined = 0;
-    double csd_last_mean = 0;
-#endif
     std::string err;
 
     int fail(int code, const char *fmt, ...) {
@@ -552,9 +535,7 @@ void drain_timing(swimsim *h) {
 }
 
 // wave-per-observer kernels (no LDS, no block barriers): SWIM_WAVE_BLOCK threads per workgroup
-#ifndef SWIM_WAVE_BLOCK
-#define SWIM_WAVE_BLOCK 256
-#endif
+constexpr uint32_t SWIM_WAVE_BLOCK = 256;
 constexpr uint32_t kWavesPerBlock = SWIM_WAVE_BLOCK / 64;
 inline uint32_t blocks_for_waves(uint32_t waves) { return waves ? (waves + kWavesPerBlock - 1) / kWavesPerBlock : 1; }
 inline uint32_t blocks_for_threads(uint32_t n) { return n ? (n + 255) / 256 : 1; }
@@ -834,106 +815,6 @@ int shard_sum(swimsim *h, uint64_t v, uint64_t *out) {
     return 0;
 }
 
-// checksums of the dirty rows selected by mode (k_list). Mode 0 (all dirty rows) hashes one row per
-// distinct content: rows are grouped by fingerprint, compared word for word with their group's first
-// row, and equal rows copy its checksum (k_fp_*).
-#ifdef SWIMSIM_DIAG
-// the reference-row path (swimsim_checksum_delta.hip) for launches of n rows (n known on the host)
-bool csd_wanted(swimsim *h, uint32_t n, CsKind kind) {
-    if (h->csd_mode == 0 || h->csd_failed || n < CSD_MIN_ROWS || h->N < 1024) return false;
-    return kind == CS_WIDE || h->csd_mode == 2;
-}
-
-int csd_alloc(swimsim *h) {
-    if (h->csd_ready) return 0;
-    h->csd_rows = h->NL;
-    h->csd_sbw_words = ((size_t)h->N * (h->W + 32) + 256) / 4;
-    int rc = 0;
-    if ((rc = dalloc(h, &h->csd_B, (size_t)h->NP, "csd reference row")) ||
-        (rc = dalloc(h, &h->csd_Lb, (size_t)h->N + 1, "csd reference lengths")) ||
-        (rc = dalloc(h, &h->csd_OB, (size_t)h->N + 1, "csd reference offsets")) ||
-        (rc = dalloc(h, &h->csd_SBw, h->csd_sbw_words, "csd reference string")) ||
-        (rc = dalloc(h, &h->csd_fb, (size_t)h->csd_rows, "csd fallback list")) ||
-        (rc = dalloc(h, &h->csd_fbcnt, 1 + CSD_NFLAGS, "csd fallback count")) ||
-        (rc = dalloc(h, &h->csd_rinfo, (size_t)h->csd_rows, "csd row info")) ||
-        (rc = dalloc(h, &h->csd_ent, (size_t)h->csd_rows * h->csd_ecap * 2, "csd exception entries"))) {
-        h->csd_failed = true;                                      // the production kernels stay in charge
-        h->err.clear();
-        return rc;
-    }
-    size_t need = 0;
-    hipcub::DeviceScan::ExclusiveSum(nullptr, need, h->csd_Lb, h->csd_OB, (int)h->N + 1, h->s);
-    if (need > h->cub_bytes) {
-        void *p = nullptr;
-        if (hipMalloc(&p, need) != hipSuccess) { h->csd_failed = true; return SWIMSIM_ENOMEM; }
-        h->allocs.push_back(p);
-        h->alloc_bytes += need;
-        h->cub_tmp = p;
-        h->cub_bytes = need;
-    }
-    h->csd_ready = true;
-    return 0;
-}
-
-// hash the n listed rows (count on the device) by the reference-row path. Returns 0 when every row is hashed, 1 when
-// the path is unavailable (the caller hashes them), < 0 on a HIP error (h->err set)
-int csd_hash(swimsim *h, const uint32_t *list, const uint32_t *cnt, uint32_t n, uint32_t dmode = 0) {
-    if (n > h->NL) return 1;
-    if (csd_alloc(h)) return 1;
-    CsdArgs a{};
-    a.B = h->csd_B;
-    a.OB = h->csd_OB;
-    a.SBw = h->csd_SBw;
-    a.sbw_words = (uint32_t)h->csd_sbw_words;
-    a.ent = h->csd_ent;
-    a.rinfo = h->csd_rinfo;
-    a.ecap = h->csd_ecap;
-    a.fb_list = h->csd_fb;
-    a.fb_cnt = h->csd_fbcnt;
-    a.dmode = dmode;
-    {
-        Scope sc(h, F_CSD_SCAN);
-        hipLaunchKernelGGL(k_csd_ref, dim3((h->N + 256) / 256), dim3(256), 0, h->s, h->d, list, n, h->csd_B, h->csd_Lb);
-        if (h->csd_maxdiff && !dmode) {
-            // rows far from the majority make many exception blocks, and the path loses to the production kernels
-            // (DESIGN.md §4): decide on a sample
-            HIPCHK(h, hipMemsetAsync(h->csd_fbcnt, 0, 4, h->s));
-            hipLaunchKernelGGL(k_csd_sample, dim3(CSD_NSAMPLE), dim3(256), 0, h->s, h->d, list, n, h->csd_B, h->csd_fbcnt);
-            HIPCHK(h, hipMemcpyAsync(h->hinfo + 16, h->csd_fbcnt, 4, hipMemcpyDeviceToHost, h->s));
-            HIPCHK(h, stream_sync(h));
-            h->csd_last_mean = (double)h->hinfo[16] / CSD_NSAMPLE;
-            if (h->csd_last_mean > (double)h->csd_maxdiff) { h->csd_declined++; return 1; }
-        }
-        size_t bytes = h->cub_bytes;
-        HIPCHK(h, hipcub::DeviceScan::ExclusiveSum(h->cub_tmp, bytes, h->csd_Lb, h->csd_OB, (int)h->N + 1, h->s));
-        HIPCHK(h, hipMemsetAsync(h->csd_SBw, 0, h->csd_sbw_words * 4, h->s));
-        launch_csd(h->d, list, n, cnt, a, h->s, 0);
-        launch_csd(h->d, list, n, cnt, a, h->s, 1);
-        HIPCHK(h, hipMemsetAsync(h->csd_fbcnt, 0, 4 * (1 + CSD_NFLAGS), h->s));
-        hipLaunchKernelGGL(k_ctr_add, dim3(1), dim3(1), 0, h->s, h->d, (int)C_X_CSD_SCANNED, (unsigned long long)n);
-    }
-    {
-        Scope sc(h, F_CS_WIDE);
-        launch_csd(h->d, list, n, cnt, a, h->s, 2);
-    }
-    h->csd_launches++;
-    // rows the path left (flags): hashed by the production kernels
-    uint32_t hf[1 + CSD_NFLAGS];
-    HIPCHK(h, hipMemcpyAsync(h->hinfo + 16, h->csd_fbcnt, 4 * (1 + CSD_NFLAGS), hipMemcpyDeviceToHost, h->s));
-    HIPCHK(h, stream_sync(h));
-    memcpy(hf, h->hinfo + 16, sizeof hf);
-    const uint32_t nf = hf[0];
-    if (nf) {
-        h->csd_fallback_rows += nf;
-        for (uint32_t b = 0; b < CSD_NFLAGS; b++) h->csd_reasons[b] += hf[1 + b];
-        const CsKind k2 = cs_kind(nf, h->cs_narrow_rows);
-        Scope sc(h, k2 == CS_WIDE ? F_CS_WIDE : F_CS_NARROW);
-        launch_checksum_kind(h->d, h->csd_fb, h->csd_fbcnt, nf, k2, h->s);
-    }
-    return 0;
-}
-#endif
-
 // the reference-row path (swimsim_checksum_csr.hip) for a launch of n rows (n known on the host)
 bool csr_wanted(swimsim *h, uint32_t n, CsKind kind) {
     if (h->csr_mode == 0 || h->csr.failed || n < CSD_MIN_ROWS || h->N < 1024) return false;
@@ -1141,12 +1022,6 @@ int hash_rows(swimsim *h, const uint32_t *list, const uint32_t *cnt, uint32_t ma
         h->csr2_used = true;
         if (rc <= 0) return rc;
     }
-#ifdef SWIMSIM_DIAG
-    if (!st && nrows != ~0u && csd_wanted(h, n, kind)) {          // diagnostics library: round 3's reference-row path
-        const int rc = csd_hash(h, list, cnt, n);
-        if (rc <= 0) return rc;                                    // done, or failed (h->err)
-    }
-#endif
     Scope sc(h, kind == CS_WIDE ? F_CS_WIDE : F_CS_NARROW, st);
     launch_checksum_kind(h->d, list, cnt, n, kind, st ? st : h->s);
     return 0;
@@ -1206,6 +1081,9 @@ int sync_side(swimsim *h) {
 // under 2 % of the one pass over them that the skipped hash would have been.
 constexpr uint32_t CS_DEFER_CHANGED_NUM = 3, CS_DEFER_CHANGED_DEN = 4, CS_DEFER_MAX_DEFERRED_DIV = 64;
 
+// checksums of the dirty rows selected by mode (k_list). Mode 0 (all dirty rows) hashes one row per
+// distinct content: rows are grouped by fingerprint, compared word for word with their group's first
+// row, and equal rows copy its checksum (k_fp_*).
 int checksum_dirty(swimsim *h, int mode, bool async = false) {
     // phase C (async) reuses side half side_gen only: the other half's launch, from the round before, may still run
     const uint32_t g = h->side_gen;
@@ -2006,10 +1884,6 @@ int swimsim_create(const swimsim_config *cfg, swimsim_t **out) {
     if (const char *v = getenv("SWIMSIM_SYNC_SPIN")) h->sync_spin = atoi(v) != 0;   // (experiment: 0 = the runtime's wait)
     if (const char *v = getenv("SWIMSIM_SIDE2"))                  // (experiment: 0 = one side stream for both generations)
         if (atoi(v) == 0 && h->side2) { hipStreamDestroy(h->side2); h->side2 = nullptr; }
-#ifdef SWIMSIM_DIAG                                 // diagnostics library only: the reference-row path
-    if (const char *v = getenv("SWIMSIM_CS_DELTA")) h->csd_mode = atoi(v);
-    if (const char *v = getenv("SWIMSIM_CS_DELTA_MAXDIFF")) h->csd_maxdiff = (uint32_t)strtoul(v, nullptr, 10);
-#endif
     DS &d = h->d;
     d.N = h->N; d.NP = h->NP; d.NL = h->NL; d.lo = h->lo;
     d.NB = h->NP / 64;
@@ -2663,21 +2537,10 @@ __global__ void k_iota(uint32_t *list, uint32_t *cnt, uint32_t n) {
 
 // mode 0: the production choice for nrows rows; 1: k_checksum3; 2: k_checksum_q16 (both production kernels); 4: the
 // wide kernel with four row groups per workgroup (k_checksum3<..., G = 4>); 5: the reference-row path (k_csd_scan,
-// k_csr and the fallback launch for rows it leaves), forced. Other modes (the reference-row path,
-// superseded kernels, diagnostic variants) exist only in the diagnostics library.
+// k_csr3 and the fallback launch for rows it leaves), forced; 6: that path as a side launch (below). Others: EINVAL.
 int swimsim_bench_checksum(swimsim_t *h, uint32_t nrows, int32_t mode, int32_t reps, double *ms) {
     if (!h || !ms || nrows == 0 || nrows > h->NL || reps < 1) return SWIMSIM_EINVAL;
-#ifndef SWIMSIM_DIAG
-    if (mode < 0 || mode > 6 || mode == 3)
-        return h->fail(SWIMSIM_EINVAL, "checksum mode %d: diagnostics build only", mode);
-    const bool csd = false;
-#else
-    // mode 3: the reference-row path (swimsim_checksum_delta.hip), its preparation and any fallback launch included;
-    // 31..46: its split modes (garbage checksums: helpers alone, hashers alone, helpers without exceptions; + 8: no
-    // barrier between super steps)
-    const bool csd = mode == 3 || (mode >= 31 && mode <= 46);
-    if (csd && (csd_alloc(h) || nrows > h->NL)) return h->fail(SWIMSIM_EINVAL, "reference-row path unavailable");
-#endif
+    if (mode < 0 || mode > 6 || mode == 3) return h->fail(SWIMSIM_EINVAL, "checksum mode %d: no such mode", mode);
     if (mode == 5 && csr_alloc(h)) return h->fail(SWIMSIM_EINVAL, "reference-row path unavailable");
     // mode 6: the reference-row path with the side-stream buffer set on the side stream, as a round-end side launch runs
     // it (nrows at most the set's rows), timed on that stream
@@ -2706,20 +2569,9 @@ int swimsim_bench_checksum(swimsim_t *h, uint32_t nrows, int32_t mode, int32_t r
     }
     int rc5 = 0;
     auto launch = [&]() {
-        if (csd) {                                                 // the path itself, never declined here
-#ifdef SWIMSIM_DIAG
-            const uint32_t keep = h->csd_maxdiff;
-            h->csd_maxdiff = 0;
-            (void)csd_hash(h, h->list, h->cnt, nrows, mode == 3 ? 0u : (uint32_t)(mode - 30));
-            h->csd_maxdiff = keep;
-#endif
-        }
-        else if (mode <= 2) launch_checksum_kind(h->d, h->list, h->cnt, nrows, mode == 0 ? cs_kind(nrows, h->cs_narrow_rows) : (CsKind)mode, h->s);
+        if (mode <= 2) launch_checksum_kind(h->d, h->list, h->cnt, nrows, mode == 0 ? cs_kind(nrows, h->cs_narrow_rows) : (CsKind)mode, h->s);
         else if (mode == 4) launch_checksum_wide4(h->d, h->list, h->cnt, nrows, h->s);
         else if (mode == 5) rc5 = csr_hash(h, h->list, h->cnt, nrows);   // the reference-row path, forced
-#ifdef SWIMSIM_DIAG
-        else launch_checksum_mode(h->d, h->list, h->cnt, nrows, mode, h->s);
-#endif
     };
     hipLaunchKernelGGL(k_iota, dim3(blocks_for_threads(nrows)), dim3(256), 0, h->s, h->list, h->cnt, nrows);
     hipEvent_t a, b;
@@ -2737,26 +2589,6 @@ int swimsim_bench_checksum(swimsim_t *h, uint32_t nrows, int32_t mode, int32_t r
     hipEventDestroy(a);
     hipEventDestroy(b);
     return check_err(h);
-}
-
-int swimsim_debug_cs_stream(swimsim_t *h, uint32_t ol, uint32_t *out, size_t cap_words) {
-    if (!h || !out || ol >= h->NL || cap_words == 0) return SWIMSIM_EINVAL;
-#ifndef SWIMSIM_DIAG
-    return h->fail(SWIMSIM_EINVAL, "swimsim_debug_cs_stream: diagnostics build only (tools/libswimsim_diag.so)");
-#else
-    uint32_t *dev = nullptr;
-    HIPCHK(h, hipMalloc(&dev, cap_words * 4));
-    HIPCHK(h, hipMemsetAsync(dev, 0xEE, cap_words * 4, h->s));
-    hipLaunchKernelGGL(k_list_one, dim3(1), dim3(64), 0, h->s, h->list, h->cnt, ol, h->d);
-    HIPCHK(h, hipMemsetAsync(h->cnt, 0, 4, h->s));
-    const uint32_t one = 1;
-    HIPCHK(h, hipMemcpyAsync(h->cnt, &one, 4, hipMemcpyHostToDevice, h->s));
-    launch_checksum_dump(h->d, h->list, h->cnt, dev, (uint32_t)cap_words, h->s);
-    HIPCHK(h, hipMemcpyAsync(out, dev, cap_words * 4, hipMemcpyDeviceToHost, h->s));
-    HIPCHK(h, stream_sync(h));
-    hipFree(dev);
-    return check_err(h);
-#endif
 }
 
 // profiler window marker: one tiny dispatch on the engine's stream, so that rocprofv3 counter passes can be cut to
@@ -3803,18 +3635,17 @@ int swimsim_kernel_units(swimsim_t *h, const char **names, double *values, size_
     if (int rc = read_counters(h, c)) return rc;
     static const char *kn[] = {"cs_rows_wide", "cs_rows_narrow", "cs_dup_rows", "recv_merged", "recv_applied",
                                "recv_issued", "recv_calls", "resp_merged", "resp_applied", "resp_bumped", "issued",
-                               "bitmap_words_per_row", "diag_stamp0", "diag_stamp1", "diag_stamp2", "diag_stamp3",
-                               "hot_slots", "diag_stamp4", "diag_stamp5", "diag_stamp6", "diag_stamp7",
-                               "dense_resp", "dense_jobs", "jobs_applied", "dense_heal", "defer", "defer_eq", "defer_norow",
-                               "defer_rep", "defer_undo", "defer_rep_diff", "defer_undo_diff", "defer_fs",
-                               "defer_undo_over", "defer_clean", "issue_snaps", "lazy_late", "lazy_mat",
+                               "bitmap_words_per_row", "hot_slots", "dense_resp", "dense_jobs", "jobs_applied",
+                               "dense_heal", "defer", "defer_eq", "defer_norow", "defer_rep", "defer_undo",
+                               "defer_rep_diff", "defer_undo_diff", "defer_fs", "defer_undo_over", "defer_clean",
+                               "issue_snaps", "lazy_late", "lazy_mat",
                                "cs_skipped_rounds", "cs_carried_rows", "cs_forced"};
     const int ki[] = {C_X_CS_ROWS, C_X_CS_ROWS_N, C_X_CS_DUP, C_X_MERGED, C_X_APPLIED, C_X_RISSUED, C_X_RCALLS,
-                      C_X_MERGED_R, C_X_APPLIED_R, C_X_BUMPED, C_X_ISSUED, -1, C_NALL, C_NALL + 1, C_NALL + 2, C_NALL + 3,
-                      -2, C_NALL + 4, C_NALL + 5, C_NALL + 6, C_NALL + 7, C_X_DENSE_RESP, C_X_DENSE_JOBS, C_X_JOBS_APPLIED,
-                      C_X_DENSE_HEAL, C_X_DEFER, C_X_DEFER_EQ, C_X_DEFER_NOROW, C_X_DEFER_REP, C_X_DEFER_UNDO,
-                      C_X_DEFER_REP_DIFF, C_X_DEFER_UNDO_DIFF, C_X_DEFER_FS, C_X_DEFER_UNDO_OVER, C_X_DEFER_CLEAN,
-                      C_X_ISSUE_SNAPS, C_X_LAZY_LATE, C_X_LAZY_MAT, -3, -4, -5};   // (-3..-5: lazy phase C, host counts)
+                      C_X_MERGED_R, C_X_APPLIED_R, C_X_BUMPED, C_X_ISSUED, -1, -2, C_X_DENSE_RESP, C_X_DENSE_JOBS,
+                      C_X_JOBS_APPLIED, C_X_DENSE_HEAL, C_X_DEFER, C_X_DEFER_EQ, C_X_DEFER_NOROW, C_X_DEFER_REP,
+                      C_X_DEFER_UNDO, C_X_DEFER_REP_DIFF, C_X_DEFER_UNDO_DIFF, C_X_DEFER_FS, C_X_DEFER_UNDO_OVER,
+                      C_X_DEFER_CLEAN, C_X_ISSUE_SNAPS, C_X_LAZY_LATE, C_X_LAZY_MAT,
+                      -3, -4, -5};                                 // (-3..-5: lazy phase C, host counts)
     const uint64_t lazy_c[3] = {h->cs_skipped_rounds - h->cs_units_base[0], h->cs_carried_rows - h->cs_units_base[1],
                                 h->cs_forced - h->cs_units_base[2]};
     static_assert(sizeof(kn) / sizeof(kn[0]) == sizeof(ki) / sizeof(ki[0]), "one counter per name");
@@ -3977,15 +3808,7 @@ int swimsim_debug_exchange(swimsim_t *h, const uint8_t *send, const uint64_t *sb
 
 int swimsim_checksum_path_stats(swimsim_t *h, uint64_t *delta_launches, uint64_t *fallback_rows, uint64_t *reasons) {
     if (!h) return SWIMSIM_EINVAL;
-#ifdef SWIMSIM_DIAG
-    if (delta_launches) *delta_launches = h->csd_launches;
-    if (fallback_rows) *fallback_rows = h->csd_fallback_rows;
-    if (reasons) {
-        for (uint32_t b = 0; b < CSD_NFLAGS; b++) reasons[b] = h->csd_reasons[b];
-        reasons[CSD_NFLAGS] = h->csd_declined;
-    }
-#else                                       // the product's reference-row path (swimsim_checksum_csr.hip)
-    unsigned long long acc[8] = {0};
+    unsigned long long acc[8] = {0};                // the reference-row path (swimsim_checksum_csr.hip)
     for (CsrSet *c : {&h->csr, &h->csr2}) {
         if (!c->ready) continue;            // counted on the device (k_csr_fbsplit), both buffer sets
         unsigned long long a2[8];
@@ -3999,7 +3822,6 @@ int swimsim_checksum_path_stats(swimsim_t *h, uint64_t *delta_launches, uint64_t
         for (uint32_t b = 0; b < 5; b++) reasons[b] = acc[1 + b];
         for (uint32_t b = 5; b < 8; b++) reasons[b] = 0;   // (reserved)
     }
-#endif
     return SWIMSIM_OK;
 }
 

@@ -1591,9 +1591,7 @@ __device__ __forceinline__ void recv_one_pre(const DS &d, const RecvArgs &a, uin
 // launch bounds: 256 threads (SWIM_WAVE_BLOCK) and at least RECV_MIN_WAVES waves per SIMD. The receive waves are
 // gather-latency bound (each message is a chain of dependent loads: pair snapshot, record, row word, then the stores),
 // so resident waves, not registers, set the pace
-#ifndef RECV_MIN_WAVES
-#define RECV_MIN_WAVES 4
-#endif
+constexpr int RECV_MIN_WAVES = 4;
 __global__ void __launch_bounds__(256, RECV_MIN_WAVES) k_recv(DS d, RecvArgs a) {
     const uint32_t u = wave_gid();
     if (u >= a.nruns_max) return;

@@ -21,8 +21,7 @@ from dataclasses import dataclass
 import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-# SWIMSIM_LIB (diagnostics only): load another build of the library, e.g. a kernel variant under test
-LIB_PATH = os.environ.get("SWIMSIM_LIB") or os.path.join(_HERE, "libswimsim.so")
+LIB_PATH = os.path.join(_HERE, "libswimsim.so")
 
 ALIVE, SUSPECT, FAULTY, LEAVE, TOMBSTONE, UNKNOWN = 0, 1, 2, 3, 4, 7
 STATUS_NAMES = {ALIVE: "alive", SUSPECT: "suspect", FAULTY: "faulty", LEAVE: "leave", TOMBSTONE: "tombstone"}
@@ -120,8 +119,8 @@ _lib = None
 
 
 def load_library(path: str = LIB_PATH):
-    """Load libswimsim.so. Raises loudly when it is absent: the product has no fallback. SWIMSIM_LIBRARY selects
-    another build of the same ABI (tools/: the diagnostics library with the superseded checksum kernels)."""
+    """Load libswimsim.so. Raises loudly when it is absent: the product has no fallback. SWIMSIM_LIBRARY names
+    another build of the library to load instead (comparing a parent commit's build against this tree's)."""
     global _lib
     if _lib is not None:
         return _lib
@@ -169,7 +168,6 @@ def load_library(path: str = LIB_PATH):
         "swimsim_checksum_path_stats": (C.c_int, [P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), _U64P]),
         "swimsim_kernel_units": (C.c_int, [P, P, P, sz, C.POINTER(sz)]),
         "swimsim_profile_mark": (C.c_int, [P, u32]),
-        "swimsim_debug_cs_stream": (C.c_int, [P, u32, P, sz]),
         "swimsim_group_create": (C.c_int, [C.POINTER(Config), u32, P, P]),
         "swimsim_group_step": (C.c_int, [P, u32, u32, C.POINTER(Event), sz]),
         "swimsim_comm_unique_id": (C.c_int, [P, sz]),
@@ -801,8 +799,7 @@ class Cluster:
         return {"shards": g.value, "rank": r.value, "lo": lo.value, "hi": hi.value, "exchanged_bytes": xb.value,
                 "exchanges": xc.value, "exchange_host_syncs": xs.value}
 
-    # (rows the reference-row path left to the production kernels, by reason; the diagnostics library's round-3 path
-    # reports its own reasons in the same slots: entry batch in "record_cap", jump slots and window misses in 5 and 6)
+    # (rows the reference-row path left to the production kernels, by reason; the last three are reserved and 0)
     CSD_REASONS = ("short", "entry_cap", "window_plan", "record_cap", "exception_slots", "reserved5", "reserved6",
                    "declined_launches")
 
@@ -813,12 +810,6 @@ class Cluster:
                                                              rs.ctypes.data_as(_U64P)))
         return {"delta_launches": dl.value, "fallback_rows": fb.value,
                 "reasons": {k: int(v) for k, v in zip(self.CSD_REASONS, rs)}}
-
-    def debug_cs_stream(self, o, nwords):
-        """the words of every 20-byte block the checksum kernel hashes for observer o (diagnostics)"""
-        out = np.zeros(nwords, dtype=np.uint32)
-        self._chk(load_library().swimsim_debug_cs_stream(self.h, o - self.lo, out.ctypes.data, nwords))
-        return out
 
     def bench_checksum(self, nrows, mode=0, reps=3):
         ms = C.c_double()

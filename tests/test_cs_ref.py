@@ -202,7 +202,7 @@ def test_perturbed_handover_on_real_cascade_rows(roles, seed):
     so the g/f chains run ahead of the h chains (roles 2), the h chains ahead (1), a record stager (4) or a window stager
     (8) falls behind, or all of them drift (15). Every order must give the production kernels' checksums at 32,768 real
     cascade rows (swimsim_bench_checksum mode 5 against mode 0). A build with one done count shared by both kinds of
-    chain wave (-DC3_T_SHAREDDONE, round 5's race) fails this test."""
+    chain wave (round 5's race, a test build since removed) failed this test."""
     n = 32768
     wl = W.config3(n=n, rounds=21, kill_round=10)
     with closing(swimsim.Cluster(n, tuning={"fault_inject": 64 | (roles << 8) | (seed << 12)})) as c:
@@ -239,6 +239,29 @@ def test_colx_rebuild_after_raw_writes_every_round():
         bad = np.nonzero(eng.checksums() != ora.checksums())[0]
         assert len(bad) == 0, f"round {r}: {len(bad)} checksums differ, first rows {bad[:5]}"
         assert eng.digest() == ora.digest(), f"round {r}: state digest differs"
+
+
+def test_removed_bench_modes_are_einval_and_leave_the_handle_usable():
+    """swimsim_bench_checksum takes modes 0, 1, 2, 4, 5 and 6. The modes a diagnostics build once took (3, 21, 31..46,
+    50/51, 62/63) and out-of-range ones are SWIMSIM_EINVAL, and after a run of refusals the production choice (mode 0)
+    and the reference-row path (mode 5) still hash 1,024 rows of a cascade to the oracle's checksums."""
+    wl = W.config3(n=1024, rounds=13, kill_round=5)
+    ora = OracleSim(wl.n)
+    eng = swimsim.Cluster(wl.n)
+    try:
+        for r in range(12):
+            ev = wl.events_for(r)
+            eng.step(1, ev)
+            ora.step(ev)
+        for mode in (3, 21, 31, 46, 50, 62, -1, 7):
+            with pytest.raises(swimsim.SwimsimError, match="EINVAL"):
+                eng.bench_checksum(64, mode)
+        want = ora.checksums()
+        for mode in (0, 5):
+            eng.bench_checksum(1024, mode, reps=1)
+            assert (eng.checksums() == want).all(), f"mode {mode}"
+    finally:
+        eng.close()
 
 
 def test_side_stream_path_on_real_cascade_rows():

@@ -1,9 +1,9 @@
 """Checksum-kernel microbench on real cascade rows (diagnostic, not the bench): config 3 at N members is run to
 round R (inside the suspect wave, where every row is dirty and the rows differ in which suspects they hold),
 then each checksum mode is timed over the first `rows` rows for every row count given (swimsim_bench_checksum
-modes: 0 = the production choice for that many rows, 1 = k_checksum3, 2 = k_checksum_q16; the diagnostics library
-(SWIMSIM_LIBRARY=tools/libswimsim_diag.so) adds 21 = k_checksum3, 50/51 = k_checksum5 with the record-tail prefetch
-1/2 steps ahead, ...). Every launch's checksums are compared with the engine's own (mismatch counts).
+modes: 0 = the production choice for that many rows, 1 = k_checksum3, 2 = k_checksum_q16, 4 = k_checksum3 with four
+row groups per workgroup, 5 = the reference-row path forced, 6 = the same as a side-stream launch). Every launch's
+checksums are compared with the engine's own (mismatch counts).
 Usage: cs_bench_real.py N R modes reps [rows,rows,...]"""
 import json
 import os
@@ -30,9 +30,6 @@ for rows in rows_list:
     for mode in modes:
         out[f"rows{rows}_mode{mode}_ms"] = round(c.bench_checksum(rows, mode, reps=reps), 3)
         out[f"rows{rows}_mode{mode}_mismatch"] = int((c.checksums()[:rows] != ref[:rows]).sum())
-        if mode in (3, 5):
+        if mode == 5:
             out[f"rows{rows}_mode{mode}_path"] = c.checksum_path_stats()
-        if mode == 3:
-            ku = c.kernel_units()
-            out["diag"] = [hex(int(ku.get(f"diag_stamp{i}", 0))) for i in range(4)]
         print(json.dumps(out), flush=True)
