@@ -25,7 +25,11 @@
 //                   appends what its waves hold with one cursor bump at the end (a wave whose buffer fills flushes
 //                   alone, one bump per wave). The host sorts and run-length encodes the pairs, so the result does
 //                   not depend on the order of arrival.
-//   k_route_n       the same two stages, then LookupN per key: the n distinct owners in walk order (below).
+//   k_route_n       the same frame, with LookupN per key: the n distinct owners in walk order (below).
+// The frame both kernels stand in: route_pick_row (the workgroup's row, or nothing to do), stages 1 and 2
+// (route_stage_bitmap, route_stage_list; route_goes_direct chooses the path), and in census mode route_stage_put (a
+// wave stages its exception pairs and flushes alone when full) and route_stage_finish (one cursor bump per workgroup).
+// Only the search of one key differs.
 // The kernels only read mw and live, on the main stream (as the census).
 #pragma once
 #include "swimsim_device.h"
@@ -120,6 +124,62 @@ __device__ __forceinline__ void route_flush(const RouteArgs &a, const unsigned l
         if (at + i < a.exc_cap) a.exc[at + i] = stage[i];
 }
 
+// The row of this workgroup; false when it has nothing to do: in census mode the base row and the rows that do not count.
+// The caller returns at once: a whole-workgroup return before any barrier.
+template <bool CENSUS>
+__device__ __forceinline__ bool route_pick_row(const DS &d, const RouteArgs &a, uint32_t &row) {
+    if (CENSUS) {
+        row = blockIdx.x;
+        if (row == a.skip_row || !(a.all || d.live[d.lo + row])) return false;
+    } else {
+        row = a.rows[blockIdx.x];
+    }
+    return row < d.NL;
+}
+
+// a row of cnt servers takes the direct path: it fits the list, and mode 2 asks for it or mode 0 finds it cheaper
+__device__ __forceinline__ bool route_goes_direct(uint32_t cnt, const RouteArgs &a, uint32_t N) {
+    return cnt <= ROUTE_LIST_CAP && (a.mode == 2u || (a.mode == 0u && (uint64_t)cnt * cnt * a.R <= N));
+}
+
+// Census: the lanes with `is` append pair() to the wave's stage, in lane order; nx, the pairs the wave holds, stays
+// wave-uniform. Call it from wave-uniform control flow only (it ballots), with nx <= ROUTE_STAGE - 64: a wave that has no
+// room for another 64 pairs afterwards flushes alone. pair is a callable: only the lanes with `is` evaluate it, after
+// the ballot. below = (1 << lane) - 1, the lanes before this one: the kernel computes it once, outside its key loop.
+template <typename Pair>
+__device__ __forceinline__ void route_stage_put(const RouteArgs &a, unsigned long long *stage, uint32_t &nx, bool is, Pair pair,
+                                                uint32_t lane, unsigned long long below) {
+    const unsigned long long mask = __ballot(is);
+    if (!mask) return;
+    if (is) stage[nx + (uint32_t)__popcll(mask & below)] = pair();
+    nx += (uint32_t)__popcll(mask);
+    if (nx > ROUTE_STAGE - 64) {
+        route_fence_lanes();
+        route_flush(a, stage, nx, route_bump(a.cursor, nx, lane), lane);
+        route_fence_lanes();
+        nx = 0;
+    }
+}
+
+// Census, the whole workgroup after its last key step: what the waves still hold is appended with one cursor bump.
+// xcnt: ROUTE_THREADS / 64 words; xat: one word.
+__device__ __forceinline__ void route_stage_finish(const RouteArgs &a, const unsigned long long (*xbuf)[ROUTE_STAGE], uint32_t *xcnt,
+                                                   unsigned long long *xat, uint32_t nx) {
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    if (lane == 0) xcnt[wave] = nx;
+    __syncthreads();
+    if (tid == 0) {
+        uint32_t tot = 0;
+#pragma unroll
+        for (uint32_t v = 0; v < ROUTE_THREADS / 64; v++) tot += xcnt[v];
+        *xat = tot ? atomicAdd(a.cursor, (unsigned long long)tot) : 0ull;
+    }
+    __syncthreads();
+    unsigned long long at = *xat;
+    for (uint32_t v = 0; v < wave; v++) at += xcnt[v];
+    route_flush(a, xbuf[wave], nx, at, lane);
+}
+
 // Stage 1 of a routed row (the whole workgroup, ROUTE_THREADS threads): stream the row's words and ballot status <= suspect
 // into the presence bitmap route_bm (route_bitmap_bytes(NP) of LDS). Returns cnt, the row's servers. wcnt: ROUTE_THREADS / 64 words.
 __device__ __forceinline__ uint32_t route_stage_bitmap(const DS &d, uint32_t row, unsigned long long *route_bm, uint32_t *wcnt) {
@@ -210,18 +270,11 @@ __global__ void __launch_bounds__(ROUTE_THREADS) k_route(DS d, RouteArgs a) {
     __shared__ unsigned long long xat;
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
     uint32_t row;
-    if (CENSUS) {
-        row = blockIdx.x;
-        if (row == a.skip_row || !(a.all || d.live[d.lo + row])) return;      // (the whole workgroup)
-    } else {
-        row = a.rows[blockIdx.x];
-    }
-    if (row >= d.NL) return;
+    if (!route_pick_row<CENSUS>(d, a, row)) return;                    // (the whole workgroup, before any barrier)
     // ---- 1. the presence bitmap of the row ----
     const uint32_t cnt = route_stage_bitmap(d, row, route_bm, wcnt);
     // ---- 2. sparse rows: the present members as a list, ascending ----
-    const bool direct = cnt != 0 && cnt <= ROUTE_LIST_CAP &&
-                        (a.mode == 2u || (a.mode == 0u && (uint64_t)cnt * cnt * a.R <= d.N));
+    const bool direct = cnt != 0 && route_goes_direct(cnt, a, d.N);
     if (direct) route_stage_list(d, route_bm, list, tpre);             // (the whole workgroup)
     // ---- 3. one thread per key ----
     const unsigned long long below = (1ull << lane) - 1ull;
@@ -255,35 +308,12 @@ __global__ void __launch_bounds__(ROUTE_THREADS) k_route(DS d, RouteArgs a) {
         }
         if (!CENSUS) {
             if (valid) a.owners[(size_t)blockIdx.x * a.K + k] = own;
-        } else {
-            const bool diff = valid && own != a.base[k];
-            const unsigned long long mask = __ballot(diff);
-            if (mask) {                                                // (wave-uniform; nx <= 64 here)
-                if (diff) xbuf[wave][nx + (uint32_t)__popcll(mask & below)] = ((unsigned long long)k << 32) | (uint32_t)(own + 1);
-                nx += (uint32_t)__popcll(mask);
-                if (nx > ROUTE_STAGE - 64) {                           // no room for another step: the wave flushes alone
-                    route_fence_lanes();
-                    route_flush(a, xbuf[wave], nx, route_bump(a.cursor, nx, lane), lane);
-                    route_fence_lanes();
-                    nx = 0;
-                }
-            }
+        } else {                                                       // (every lane is here: one put per key step)
+            route_stage_put(a, xbuf[wave], nx, valid && own != a.base[k],
+                            [&] { return ((unsigned long long)k << 32) | (uint32_t)(own + 1); }, lane, below);
         }
     }
-    if (CENSUS) {                                                      // what the waves still hold: one bump per workgroup
-        if (lane == 0) xcnt[wave] = nx;
-        __syncthreads();
-        if (tid == 0) {
-            uint32_t tot = 0;
-#pragma unroll
-            for (uint32_t v = 0; v < ROUTE_THREADS / 64; v++) tot += xcnt[v];
-            xat = tot ? atomicAdd(a.cursor, (unsigned long long)tot) : 0ull;
-        }
-        __syncthreads();
-        unsigned long long at = xat;
-        for (uint32_t v = 0; v < wave; v++) at += xcnt[v];
-        route_flush(a, xbuf[wave], nx, at, lane);
-    }
+    if (CENSUS) route_stage_finish(a, xbuf, xcnt, &xat, nx);
 }
 
 // ---- replica sets: LookupN through every observer's view (swimsim_route_n / swimsim_replica_census) ----
@@ -292,7 +322,7 @@ __global__ void __launch_bounds__(ROUTE_THREADS) k_route(DS d, RouteArgs a) {
 // wrapping once, each at its first occurrence; a view of cnt <= n servers lists all of them in ascending member index
 // (include/swimsim.h). A point is real only for the lowest present member at its hash: pts and hm hold an entry for
 // every member, so when present members a < b share a hash, b's entry is no point of this view and must not list b.
-//   k_route_n   stages 1 and 2 of k_route (the presence bitmap, the ascending list), then one thread per key:
+//   k_route_n   the frame of k_route (the row pick, the presence bitmap, the ascending list), then one thread per key:
 //     cnt <= n  the list itself (n <= ROUTE_NN_MAX <= ROUTE_LIST_CAP: such a row always fits the list);
 //     walk      from p0 along pts, the whole 8-byte point. A point whose member is present is taken unless its hash
 //               equals the hash of the last present point seen (equal hashes are contiguous in pts, member ascending,
@@ -341,16 +371,10 @@ __global__ void __launch_bounds__(ROUTE_THREADS) k_route_n(DS d, RouteNArgs an) 
     const uint32_t n = an.n;
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
     uint32_t row;
-    if (CENSUS) {
-        row = blockIdx.x;
-        if (row == a.skip_row || !(a.all || d.live[d.lo + row])) return;      // (the whole workgroup)
-    } else {
-        row = a.rows[blockIdx.x];
-    }
-    if (row >= d.NL) return;
+    if (!route_pick_row<CENSUS>(d, a, row)) return;                    // (the whole workgroup, before any barrier)
     const uint32_t cnt = route_stage_bitmap(d, row, route_bm, wcnt);
     const bool small = cnt <= n;                                       // every server, ascending: the list
-    const bool direct = !small && cnt <= ROUTE_LIST_CAP && (a.mode == 2u || (a.mode == 0u && (uint64_t)cnt * cnt * a.R <= d.N));
+    const bool direct = !small && route_goes_direct(cnt, a, d.N);
     if (cnt != 0 && (small || direct)) route_stage_list(d, route_bm, list, tpre);   // (the whole workgroup)
     if (!CENSUS && tid == 0 && an.servers) an.servers[blockIdx.x] = cnt;
     const uint32_t want = min(n, cnt);
@@ -434,42 +458,20 @@ __global__ void __launch_bounds__(ROUTE_THREADS) k_route_n(DS d, RouteNArgs an) 
                 }
             }
             if (__ballot((plus | minus) != 0u)) {                      // (wave-uniform)
-                for (uint32_t s = 0; s < 2u * n; s++) {
+                for (uint32_t s = 0; s < 2u * n; s++) {                // (one put per slot: each adds up to 64 pairs)
                     const bool sign = s >= n;
                     const uint32_t i = sign ? s - n : s;
-                    const bool is = ((sign ? minus : plus) >> i) & 1u;
-                    const unsigned long long mask = __ballot(is);
-                    if (!mask) continue;                               // (wave-uniform; nx <= ROUTE_STAGE - 64 here)
-                    if (is) {
-                        const uint32_t m = sign ? (uint32_t)bp[i] : mine[i * ROUTE_THREADS];
-                        xbuf[wave][nx + (uint32_t)__popcll(mask & below)] =
-                            ((unsigned long long)k << 32) | ((unsigned long long)(m + 1u) << 1) | (sign ? 1ull : 0ull);
-                    }
-                    nx += (uint32_t)__popcll(mask);
-                    if (nx > ROUTE_STAGE - 64) {                       // no room for another slot: the wave flushes alone
-                        route_fence_lanes();
-                        route_flush(a, xbuf[wave], nx, route_bump(a.cursor, nx, lane), lane);
-                        route_fence_lanes();
-                        nx = 0;
-                    }
+                    // (the slot's member: base member i or my member i; one pointer, read only by the lanes that stage)
+                    const uint32_t *src = sign ? reinterpret_cast<const uint32_t *>(bp) + i : mine + i * ROUTE_THREADS;
+                    route_stage_put(a, xbuf[wave], nx, ((sign ? minus : plus) >> i) & 1u, [&] {
+                        const uint32_t m = *src;
+                        return ((unsigned long long)k << 32) | ((unsigned long long)(m + 1u) << 1) | (sign ? 1ull : 0ull);
+                    }, lane, below);
                 }
             }
         }
     }
-    if (CENSUS) {                                                      // what the waves still hold: one bump per workgroup
-        if (lane == 0) xcnt[wave] = nx;
-        __syncthreads();
-        if (tid == 0) {
-            uint32_t tot = 0;
-#pragma unroll
-            for (uint32_t v = 0; v < ROUTE_THREADS / 64; v++) tot += xcnt[v];
-            xat = tot ? atomicAdd(a.cursor, (unsigned long long)tot) : 0ull;
-        }
-        __syncthreads();
-        unsigned long long at = xat;
-        for (uint32_t v = 0; v < wave; v++) at += xcnt[v];
-        route_flush(a, xbuf[wave], nx, at, lane);
-    }
+    if (CENSUS) route_stage_finish(a, xbuf, xcnt, &xat, nx);
 }
 
 }  // namespace swimdev

@@ -645,17 +645,23 @@ class Cluster:
         w = _census_who(who, "route_census")
         blob, off = _pack_keys(keys)
         K = len(off) - 1
-        cap = max(1, 2 * K)
+        return self._census_retry(load_library().swimsim_route_census,
+                                  (blob, off.ctypes.data, K, int(replica_points), w, int(mode)), max(1, 2 * K))
+
+    def _census_retry(self, fn, lead, cap):
+        """(counted, hist_off, hist_member, hist_count, ms) of the census fn(h, *lead, outputs ...), lead = the packed
+        keys, their offsets, K and the call's own arguments: called with buffers of cap entries and again with as many as
+        it reports until every entry fits"""
+        K = lead[2]
         while True:
             hoff = np.zeros(K + 1, np.uint64)
-            own = np.empty(cap, np.int32)
+            mem = np.empty(cap, np.int32)
             cnt = np.empty(cap, np.uint32)
             counted, nh, ms = C.c_uint32(), C.c_size_t(), C.c_double()
-            self._chk(load_library().swimsim_route_census(self.h, blob, off.ctypes.data, K, int(replica_points), w,
-                                                          int(mode), C.byref(counted), hoff.ctypes.data, own.ctypes.data,
-                                                          cnt.ctypes.data, cap, C.byref(nh), C.byref(ms)))
+            self._chk(fn(self.h, *lead, C.byref(counted), hoff.ctypes.data, mem.ctypes.data, cnt.ctypes.data, cap,
+                         C.byref(nh), C.byref(ms)))
             if nh.value <= cap:
-                return counted.value, hoff, own[:nh.value].copy(), cnt[:nh.value].copy(), ms.value
+                return counted.value, hoff, mem[:nh.value].copy(), cnt[:nh.value].copy(), ms.value
             cap = nh.value
 
     # ---- replica sets through the observers' own ring views (swimsim_route_n / swimsim_replica_census) ----
@@ -686,19 +692,8 @@ class Cluster:
         w = _census_who(who, "replica_census")
         blob, off = _pack_keys(keys)
         K = len(off) - 1
-        cap = max(1, 2 * n * K)
-        while True:
-            hoff = np.zeros(K + 1, np.uint64)
-            mem = np.empty(cap, np.int32)
-            cnt = np.empty(cap, np.uint32)
-            counted, nh, ms = C.c_uint32(), C.c_size_t(), C.c_double()
-            self._chk(load_library().swimsim_replica_census(self.h, blob, off.ctypes.data, K, int(replica_points), n, w,
-                                                            int(mode), C.byref(counted), hoff.ctypes.data,
-                                                            mem.ctypes.data, cnt.ctypes.data, cap, C.byref(nh),
-                                                            C.byref(ms)))
-            if nh.value <= cap:
-                return counted.value, hoff, mem[:nh.value].copy(), cnt[:nh.value].copy(), ms.value
-            cap = nh.value
+        return self._census_retry(load_library().swimsim_replica_census,
+                                  (blob, off.ctypes.data, K, int(replica_points), n, w, int(mode)), max(1, 2 * n * K))
 
     def address(self, m):
         """member m's address (the synthetic one unless the cluster was given addresses)"""
@@ -972,17 +967,22 @@ class ShardedCluster:
         return rounds, nlive, counts, max(p[3] for p in parts)
 
     # key routing over all shards: route goes to the shards that own the observers, histograms add per (key, owner)
-    def route(self, keys, observers, replica_points=100, mode=0):
+    def _observer_shards(self, observers, what):
+        """(obs, [(shard, sel)]): the observers as an index array, refused when there are none or one is out of range,
+        and for every shard that owns some of them their positions in obs"""
         obs = _member_list(observers)
         if len(obs) and obs.max() >= self.n:
-            raise SwimsimError("EINVAL: route: observer out of range")
-        out = np.empty((len(obs), len(keys)), np.int32)
+            raise SwimsimError(f"EINVAL: {what}: observer out of range")
         if not len(obs):
-            raise SwimsimError("EINVAL: route: no observers")
-        for c in self.shards:
-            sel = np.nonzero((obs >= c.lo) & (obs < c.lo + c.nl))[0]
-            if len(sel):
-                out[sel] = c.route(keys, obs[sel], replica_points, mode)
+            raise SwimsimError(f"EINVAL: {what}: no observers")
+        parts = [(c, np.nonzero((obs >= c.lo) & (obs < c.lo + c.nl))[0]) for c in self.shards]
+        return obs, [(c, sel) for c, sel in parts if len(sel)]
+
+    def route(self, keys, observers, replica_points=100, mode=0):
+        obs, parts = self._observer_shards(observers, "route")
+        out = np.empty((len(obs), len(keys)), np.int32)
+        for c, sel in parts:
+            out[sel] = c.route(keys, obs[sel], replica_points, mode)
         return out
 
     def route_census(self, keys, who="live", replica_points=100, mode=0):
@@ -990,17 +990,11 @@ class ShardedCluster:
 
     def route_n(self, keys, observers, n=3, replica_points=100, mode=0):
         n = _replica_n(n, "route_n")
-        obs = _member_list(observers)
-        if len(obs) and obs.max() >= self.n:
-            raise SwimsimError("EINVAL: route_n: observer out of range")
-        if not len(obs):
-            raise SwimsimError("EINVAL: route_n: no observers")
+        obs, parts = self._observer_shards(observers, "route_n")
         out = np.empty((len(obs), len(keys), n), np.int32)
         srv = np.empty(len(obs), np.uint32)
-        for c in self.shards:
-            sel = np.nonzero((obs >= c.lo) & (obs < c.lo + c.nl))[0]
-            if len(sel):
-                out[sel], srv[sel] = c.route_n(keys, obs[sel], n, replica_points, mode)
+        for c, sel in parts:
+            out[sel], srv[sel] = c.route_n(keys, obs[sel], n, replica_points, mode)
         return out, srv
 
     def replica_census(self, keys, n=3, who="live", replica_points=100, mode=0):

@@ -78,13 +78,15 @@ def live_mask(ora, who):
     return np.array([ora.live(o) for o in range(ora.n)], bool) if who == "live" else np.ones(ora.n, bool)
 
 
-def check_hist(got, want, what):
+def check_hist(got, want, what, per_key=None):
+    """exact, every key; the counts of a key sum to per_key (route_census: one owner per counted row)"""
     counted, off, own, cnt = got[:4]
+    per_key = want[0] if per_key is None else per_key
     assert counted == want[0], f"{what}: counted {counted}, oracle {want[0]}"
     assert (off == want[1]).all(), f"{what}: hist_off differs at key {np.nonzero(off != want[1])[0][:3]}"
-    assert (own == want[2]).all() and (cnt == want[3]).all(), f"{what}: histogram entries differ"
+    assert len(own) == len(want[2]) and (own == want[2]).all() and (cnt == want[3]).all(), f"{what}: histogram entries differ"
     for k in range(len(off) - 1):
-        assert int(cnt[int(off[k]):int(off[k + 1])].sum()) == counted
+        assert int(cnt[int(off[k]):int(off[k + 1])].sum()) == per_key
     assert got[4] >= 0
 
 
@@ -370,6 +372,52 @@ def test_full_exception_buffer_reruns_over_fewer_keys():
             assert exceptions > 300, f"{exceptions} exception pairs do not overflow a buffer of 300"
             for mode in MODES:
                 check_hist(eng.route_census(keys, who, 100, mode), expected_hist(owners, mask), f"chunked {who} {mode}")
+    finally:
+        del os.environ["SWIMSIM_ROUTE_EXC_CAP"]
+        eng.close()
+
+
+@pytest.mark.parametrize("call, nkeys, n", [("route_census", 90000, 1), ("replica_census", 30000, 2)])
+def test_more_runs_than_the_first_read_back(call, nkeys, n):
+    """The census reads the first 65,536 runs of a pass back together with their number and the rest with a second
+    copy. 64 members, converged, except row 5, which holds only six of them: with the buffer raised to 262,144 pairs
+    one pass holds every pair, and row 5 alone differs from the base (row 0) in more than 65,536 runs: a run is a
+    (key, owner != base owner) entry for route_census (81,586 of the 90,000 keys), a member of the symmetric difference
+    of the two sets for replica_census (108,880 for 30,000 keys at n = 2). The expectation is built from two oracle
+    rings, the 64 members' and the six members': every other row counts for the first, row 5 for the second."""
+    N, R, six = 64, 100, [3, 17, 22, 40, 41, 63]
+    keys = [f"k{i}" for i in range(nkeys)]
+    eng, ora = make_pair(N)
+    os.environ["SWIMSIM_ROUTE_EXC_CAP"] = "262144"
+    try:
+        st = np.full(N, swimsim.FAULTY, np.uint8)
+        st[six] = swimsim.ALIVE
+        eng.set_row(5, st, np.full(N, swimsim.T0_MS, np.int64))
+        for m in range(N):
+            ora.set_member(5, m, int(st[m]), swimsim.T0_MS)
+        ost, _ = ora.rows()
+        assert all(ora.live(o) for o in range(N))
+        assert (np.delete(ost, 5, axis=0) == swimsim.ALIVE).all() and list(np.nonzero(ost[5] <= 1)[0]) == six
+        addr = [swimsim.address_of(m) for m in range(N)]
+        index = {a: m for m, a in enumerate(addr)}
+        sets = []                                                     # [K, n] member indices under the two rings
+        for members in (range(N), six):
+            ring = OracleRing(R)
+            ring.add_remove_servers([addr[m] for m in members], [])
+            got = [[index[ring.lookup(key)[0]]] for key in keys] if call == "route_census" else \
+                  [[index[a] for a in ring.lookup_n(key, n)] for key in keys]
+            sets.append(np.array(got, np.int64))
+            assert sets[-1].shape == (nkeys, n)
+        # entries (key, member, rows): N - 1 rows answer the first ring's members, one row the second's; equal ones add
+        code = np.concatenate([(np.arange(nkeys)[:, None] * N + s).ravel() for s in sets])
+        rows = np.concatenate([np.full(nkeys * n, N - 1), np.full(nkeys * n, 1)])
+        u, inv = np.unique(code, return_inverse=True)                 # ascending by (key, member)
+        cnt = np.bincount(inv.ravel(), weights=rows).astype(np.uint32)
+        off = np.searchsorted(u // N, np.arange(nkeys + 1)).astype(np.uint64)
+        runs = int((sets[0] != sets[1]).sum()) if call == "route_census" else int((cnt != N).sum())
+        assert 65536 < runs < 262144, f"{runs} exception runs"
+        got = eng.route_census(keys, "live", R, 0) if call == "route_census" else eng.replica_census(keys, n, "live", R, 0)
+        check_hist(got, (N, off, (u % N).astype(np.int32), cnt), f"{call} with {runs} runs", per_key=N * n)
     finally:
         del os.environ["SWIMSIM_ROUTE_EXC_CAP"]
         eng.close()
