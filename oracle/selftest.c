@@ -160,6 +160,112 @@ static void ring_workload(void) {
     or_ring_free(r);
 }
 
+/* xorshift64* (Vigna 2016): the random schedule's own small generator */
+static uint64_t xs_state = 0x9E3779B97F4A7C15ULL;
+static uint32_t xs(uint32_t n) {               /* uniform enough in [0, n) */
+    xs_state ^= xs_state >> 12;
+    xs_state ^= xs_state << 25;
+    xs_state ^= xs_state >> 27;
+    return (uint32_t)(((xs_state * 0x2545F4914F6CDD1DULL) >> 33) % n);
+}
+
+/* a random schedule in the shape of tests/fuzz_scenarios.py: all eight event kinds, several events on one member in
+   one round, events on dead and departed members, raw mutators between rounds, the short timeouts (suspect 5, faulty
+   10, tombstone 5 rounds) so that the whole timer chain and evictions run. The cost-model run must keep its digests. */
+static void random_schedule(uint32_t n, uint32_t rounds) {
+    static const int32_t statuses[6] = {OR_ALIVE, OR_SUSPECT, OR_FAULTY, OR_LEAVE, OR_TOMBSTONE, OR_UNKNOWN};
+    or_config c0 = config(n, 0, 0, 11), c1 = config(n, 0, 1, 11);
+    c0.suspect_ms = c1.suspect_ms = 1000;
+    c0.faulty_ms = c1.faulty_ms = 2000;
+    c0.tombstone_ms = c1.tombstone_ms = 1000;
+    c0.max_rfs_jobs = c1.max_rfs_jobs = 1;
+    c0.ping_request_size = c1.ping_request_size = 2;
+    or_sim *s[2] = {or_create(&c0), or_create(&c1)};
+    or_change *buf = malloc(sizeof(or_change) * (size_t)(4 * n + 4096));
+    int32_t *seq = malloc(sizeof(int32_t) * (size_t)(4 * n + 4096)), *tg = malloc(sizeof(int32_t) * n);
+    uint8_t *used = malloc(n);
+    for (int k = 0; k < 2; k++) {
+        or_init_converged(s[k]);
+        or_watch(s[k], 0, 2);
+        or_watch(s[k], n - 1, 2);
+    }
+    uint32_t prev = 0;
+    for (uint32_t r = 0; r < rounds; r++) {
+        const int64_t t0 = c0.t0_ms, P = c0.period_ms;
+        for (uint32_t q = xs(3) == 0 ? 1 + xs(8) : 0; r > 0 && q > 0; q--) {   /* raw mutators before the round */
+            const uint32_t o = xs(n), m = (o + 1 + xs(n - 1)) % n, what = xs(9);
+            const int64_t inc = t0 + (int64_t)xs(r + 3) * P;
+            const int32_t st = statuses[xs(6)];
+            int32_t nj = 0;
+            if (what == 4) {                                          /* a join list of distinct members */
+                memset(used, 0, n);
+                for (uint32_t i = 1 + xs(40); i > 0; i--) {
+                    const uint32_t jm = xs(n);
+                    if (used[jm]++) continue;
+                    const int32_t src = xs(2) ? (int32_t)xs(n) : OR_SOURCE_NONE;
+                    buf[nj++] = (or_change){(int32_t)jm, statuses[xs(5)], src, 0, t0 + (int64_t)xs(r + 3) * P,
+                                            src < 0 ? 0 : t0 + (int64_t)xs(r + 3) * P};
+                }
+            }
+            const uint64_t mark = xs_state;                           /* both runs draw the same row */
+            for (int k = 0; k < 2; k++) {
+                switch (what) {
+                case 0: or_set_member(s[k], o, m, st, st == OR_UNKNOWN ? t0 : inc); break;
+                case 1: (void)or_make_change(s[k], o, xs_state % n, inc, st == OR_UNKNOWN ? OR_ALIVE : st); break;
+                case 2: or_clear_changes(s[k], o); break;
+                case 3:
+                    xs_state = mark;
+                    for (uint32_t x = 0; x < n; x++) {
+                        const int32_t rs = x == o ? OR_ALIVE : statuses[xs(6)];
+                        or_set_member(s[k], o, x, rs, rs == OR_UNKNOWN ? t0 : t0 + (int64_t)xs(r + 3) * P);
+                    }
+                    break;
+                case 4: (void)or_add_join_list(s[k], o, buf, nj); break;
+                case 5: or_set_live(s[k], o, (int32_t)(mark & 1)); break;
+                case 6: or_set_partition(s[k], o, (int32_t)(mark % 3)); break;
+                case 7: or_set_clock_offset(s[k], o, ((int64_t)(mark % 7) - 3 < -(int64_t)r ? -(int64_t)r : (int64_t)(mark % 7) - 3) * P); break;
+                case 8: (void)or_heal(s[k], o, tg, (int32_t)n); break;
+                }
+            }
+        }
+        or_event ev[8];
+        static const uint32_t counts[7] = {0, 0, 1, 1, 2, 3, 6};
+        const uint32_t nev = counts[xs(7)] + (r == 20 || r == 45);
+        for (uint32_t i = 0; i < nev; i++) {
+            const uint32_t a = xs(10) < 3 ? prev : xs(n);
+            const uint32_t kind = (r == 20 || r == 45) && i + 1 == nev ? OR_EV_CLOCK : 1 + xs(8);
+            int32_t b = kind == OR_EV_PARTITION ? (int32_t)xs(3) : 0;
+            if (kind == OR_EV_CLOCK) {
+                b = i + 1 == nev && r == 20 ? 30 : i + 1 == nev && r == 45 ? -30 : (int32_t)xs(7) - 3;
+                if ((int64_t)r + b < 0) b = -(int32_t)r;
+            }
+            prev = a;
+            ev[i] = (or_event){r, kind, (int32_t)a, b};
+        }
+        for (int k = 0; k < 2; k++) or_step(s[k], ev, nev);
+        uint64_t d[2][3];
+        for (int k = 0; k < 2; k++) or_digest(s[k], &d[k][0], &d[k][1], &d[k][2]);
+        CHECK(!memcmp(d[0], d[1], sizeof d[0]), "random schedule: round %u: the cost-model run's digests differ", r);
+        for (uint32_t o = 0; o < n; o += 7) {
+            CHECK(or_checksum(s[0], o) == or_checksum(s[1], o), "random schedule: round %u observer %u: checksums", r, o);
+            (void)or_dis_entries(s[0], o, seq, seq + n, seq + 2 * n, (int64_t *)buf, (int32_t)n);
+            (void)or_num_pingable(s[0], o);
+            (void)or_clock_offset(s[0], o);
+        }
+        uint32_t ocs, ncs;
+        int32_t nm;
+        (void)or_drain_events(s[0], 0, buf, seq, (int32_t)(4 * n + 4096), &ocs, &ncs, &nm);
+        (void)or_drain_events(s[0], n - 1, buf, seq, (int32_t)(4 * n + 4096), &ocs, &ncs, &nm);
+    }
+    uint64_t ctr[OR_NCOUNTERS];
+    or_counters(s[0], ctr);
+    CHECK(ctr[OR_C_TIMERS_FIRED] > 0 && ctr[OR_C_FULL_SYNCS] > 0 && ctr[OR_C_REFUTES] > 0,
+          "random schedule: timers %llu, full syncs %llu, refutes %llu", (unsigned long long)ctr[OR_C_TIMERS_FIRED],
+          (unsigned long long)ctr[OR_C_FULL_SYNCS], (unsigned long long)ctr[OR_C_REFUTES]);
+    for (int k = 0; k < 2; k++) or_destroy(s[k]);
+    free(buf); free(seq); free(tg); free(used);
+}
+
 int main(void) {
     /* Fingerprint32 on every length path (0..4, 5..12, 13..24, > 24) */
     uint8_t bytes[200];
@@ -192,6 +298,8 @@ int main(void) {
     run_workload("partition", 32, 0, part, np, 70, 0);
     /* self-only start: full syncs and reverse full syncs */
     run_workload("self_only", 24, 1, NULL, 0, 40, 0);
+    /* a seeded random schedule: same-round event sequences, events on dead members, raw mutators mid-run */
+    random_schedule(65, 60);
     ring_workload();
     if (failures) {
         fprintf(stderr, "selftest: %d check(s) failed\n", failures);

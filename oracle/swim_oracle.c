@@ -270,6 +270,7 @@ void or_set_member(or_sim *s, uint32_t o, uint32_t m, int32_t status, int64_t in
 }
 
 void or_set_clock_offset(or_sim *s, uint32_t o, int64_t off) { s->o[o].clock_off = off; }
+int64_t or_clock_offset(const or_sim *s, uint32_t o) { return s->o[o].clock_off; }
 void or_set_live(or_sim *s, uint32_t o, int32_t live) { s->o[o].live = live; }
 void or_set_partition(or_sim *s, uint32_t o, int32_t label) { s->o[o].part = label; }
 void or_set_round(or_sim *s, uint32_t r) { s->round = r; }
@@ -993,6 +994,7 @@ static void apply_event(or_sim *s, const or_event *e) {
             for (uint32_t m = 0; m < s->n; m++)
                 if (ST(s, a, m) == OR_FAULTY) or_make_change(s, a, m, INC(s, a, m), OR_TOMBSTONE);
         break;
+    case OR_EV_CLOCK: s->o[a].clock_off = (int64_t)e->b * s->cfg.period_ms; break;  /* ROUND_SEMANTICS §4 E */
     }
 }
 

@@ -55,7 +55,8 @@ typedef struct or_config {
 
 enum {
     OR_EV_KILL = 1, OR_EV_REVIVE = 2, OR_EV_REINCARNATE = 3, OR_EV_LEAVE = 4,
-    OR_EV_PARTITION = 5, OR_EV_HEAL = 6, OR_EV_REAP = 7
+    OR_EV_PARTITION = 5, OR_EV_HEAL = 6, OR_EV_REAP = 7,
+    OR_EV_CLOCK = 8      /* clock_off(a) = b periods, in list order (a clock step between two events of a round) */
 };
 typedef struct or_event { uint32_t round; uint32_t kind; int32_t a; int32_t b; } or_event;
 
@@ -76,6 +77,7 @@ void or_init_converged(or_sim *s);          /* every row: all alive @ t0, maxP =
 void or_init_self_only(or_sim *s);          /* every row: only self alive @ t0, maxP = pFactor */
 void or_set_member(or_sim *s, uint32_t o, uint32_t m, int32_t status, int64_t inc);
 void or_set_clock_offset(or_sim *s, uint32_t o, int64_t off_ms);
+int64_t or_clock_offset(const or_sim *s, uint32_t o);
 void or_set_live(or_sim *s, uint32_t o, int32_t live);
 void or_set_partition(or_sim *s, uint32_t o, int32_t label);
 void or_set_round(or_sim *s, uint32_t r);

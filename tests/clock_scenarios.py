@@ -37,8 +37,9 @@ def s_events_with_clock_events():
 
 
 def oracle_step(ora, events):
-    """one oracle round of an event list that may hold EV_CLOCK events: the oracle has no such event, so they are
-    stripped and set through set_clock_offset before the round (each comes first in its round's list)"""
+    """one oracle round of an event list that may hold EV_CLOCK events: they are stripped and set through
+    set_clock_offset before the round (each comes first in its round's list), which checks the engine's event against
+    the setter; the oracle's own OR_EV_CLOCK is what tests/test_fuzz.py runs"""
     r = ora.round
     for (er, k, a, b) in events:
         if er == r and k == swimsim.EV_CLOCK:

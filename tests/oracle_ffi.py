@@ -19,6 +19,7 @@ OMP_LIB_PATH = os.path.join(ORACLE_DIR, "build", "libswim_oracle_omp.so")
 ALIVE, SUSPECT, FAULTY, LEAVE, TOMBSTONE, UNKNOWN = 0, 1, 2, 3, 4, 7
 SOURCE_NONE = -1
 EV_KILL, EV_REVIVE, EV_REINCARNATE, EV_LEAVE, EV_PARTITION, EV_HEAL, EV_REAP = 1, 2, 3, 4, 5, 6, 7
+EV_CLOCK = 8                                     # (r, EV_CLOCK, observer, offset in periods), applied in list order
 COUNTER_NAMES = [
     "rounds", "pings", "pings_ok", "pingreqs", "helper_calls", "helper_errors", "inconclusive",
     "suspect_decl", "applied", "refutes", "full_syncs", "full_syncs_pingreq", "rfs_done",
@@ -69,6 +70,7 @@ def lib():
             "or_init_self_only": (None, [P]),
             "or_set_member": (None, [P, u32, u32, i32, i64]),
             "or_set_clock_offset": (None, [P, u32, i64]),
+            "or_clock_offset": (i64, [P, u32]),
             "or_set_live": (None, [P, u32, i32]),
             "or_set_partition": (None, [P, u32, i32]),
             "or_set_round": (None, [P, u32]),
@@ -216,6 +218,24 @@ class OracleSim:
 
     def set_clock_offset(self, o, off):
         lib().or_set_clock_offset(self.h, o, off)
+
+    def clock_offsets(self):
+        """the clock offsets in force, in ms (length n)"""
+        return np.array([lib().or_clock_offset(self.h, o) for o in range(self.n)], dtype=np.int64)
+
+    def set_row(self, o, status, inc):
+        """raw write of observer o's whole row, as Cluster.set_row: a loop over or_set_member. A non-member (UNKNOWN)
+        takes incarnation t0, which is what the engine's row word of a non-member holds (e = 0)."""
+        for m in range(self.n):
+            st = int(status[m])
+            lib().or_set_member(self.h, o, m, st, self.t0_ms if st == UNKNOWN else int(inc[m]))
+
+    def add_join_list(self, o, member, status, inc, source=None, source_inc=None):
+        """memberlist.AddJoinList in the column form of Cluster.add_join_list; returns the number of applied changes"""
+        chs = [(int(member[i]), int(status[i]), int(inc[i]),
+                SOURCE_NONE if source is None else int(source[i]), 0 if source_inc is None else int(source_inc[i]))
+               for i in range(len(member))]
+        return self.add_join_list_changes(o, chs)
 
     def set_live(self, o, live):
         lib().or_set_live(self.h, o, int(live))
