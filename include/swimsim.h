@@ -465,7 +465,9 @@ int swimsim_checksum_path_stats(swimsim_t *h, uint64_t *delta_launches, uint64_t
  * [N*r/G, N*(r+1)/G) of one simulated cluster and exchanges every cross-shard message (ping
  * requests and responses, ping-req relays, reverse-full-sync and heal memberships) with the other
  * shards at fixed points of the round. With G > 1 swimsim_step() is collective: every shard calls
- * it with the same events. Results stay bit-identical to G = 1. */
+ * it with the same events. Results stay bit-identical to G = 1. The coverage of the checksum tables is
+ * agreed at each step call: a raw write (set_member, set_row, make_change, add_join_list) grows the
+ * tables of the shard that owns the row, and the others grow to the largest before a round runs. */
 /* G shards in this process (one thread each in swimsim_group_step), all on cfg->device or on
  * devices[i]; copies between shards are device-to-device (peer copies across GPUs) */
 int swimsim_group_create(const swimsim_config *cfg, uint32_t nshards, const int32_t *devices, swimsim_t **out);

@@ -2183,6 +2183,7 @@ int swimsim_make_change(swimsim_t *h, uint32_t o, uint32_t m, int64_t inc_ms, in
     if (!h || !own(h, o) || m >= h->N || status < 0 || status > 4) return SWIMSIM_EINVAL;
     uint32_t e;
     if (int rc = to_e(h, inc_ms, &e)) return rc;
+    if (int rc = ensure_ecap(h, e)) return rc;                  // the checksum tables cover the new incarnation
     std::vector<uint4> b{make_uint4(1, o, m, e | ((uint32_t)status << 29))};
     if (int rc = flush_events(h, b)) return rc;
     uint32_t applied = 0;
@@ -2295,6 +2296,21 @@ int swimsim_clock_offsets(swimsim_t *h, int64_t *out) {
     return SWIMSIM_OK;
 }
 
+// A raw write (set_member, set_row, make_change, add_join_list) grows the tables of the handle that owns the row; the
+// round's traffic then carries the incarnation to the other shards' rows, whose checksum kernels clamp what their own
+// tables do not hold. So the shards agree on the largest table before any round of a step call hashes anything: raw
+// writes happen between step calls only, and growth inside a call follows the round and the clock table, which every
+// shard holds in full. The shards of one process are grown by swimsim_group_step; an attached handle exchanges its
+// ecap through the transport's size exchange (every shard calls this at the same place of swimsim_step).
+static int agree_ecap(swimsim *h) {
+    if (h->G == 1 || dynamic_cast<LocalPort *>(h->xp.get())) return 0;
+    std::vector<uint64_t> send(h->G, h->ecap), recv(h->G);
+    if (int rc = h->xp->sizes(send.data(), recv.data(), 1)) return h->fail(rc, "shard table exchange failed (%s)", h->xp->name());
+    const uint64_t want = *std::max_element(recv.begin(), recv.end());
+    if (want > kMaxEcap) return h->fail(SWIMSIM_ERANGE, "a shard reports a checksum table of %llu steps", (unsigned long long)want);
+    return ensure_ecap(h, (uint32_t)want - 1);                     // (tables double from one configured size: to `want`)
+}
+
 int swimsim_step(swimsim_t *h, uint32_t nrounds, const swimsim_event *events, size_t nevents) {
     if (!h) return SWIMSIM_EINVAL;
     if (h->G == 1 && h->NL != h->N) return h->fail(SWIMSIM_EINVAL, "a partial observer range needs a shard transport");
@@ -2308,6 +2324,8 @@ int swimsim_step(swimsim_t *h, uint32_t nrounds, const swimsim_event *events, si
         if (int rc = check_clock_offset(h, (uint32_t)e.a, e.b, e.round)) return rc;
         ev_kmax = std::max(ev_kmax, e.b);
     }
+    if (nrounds)
+        if (int rc = agree_ecap(h)) return rc;
     if (h->colx_stale && nrounds) {                                // (no snapshot is alive between step calls)
         // the rebuild reads the live rows only: every step call ends with the side stream drained, and dense snapshots
         // live within one round, so none can hold a word the rebuilt bitmap would not cover
@@ -3143,6 +3161,22 @@ int swimsim_group_create(const swimsim_config *cfg, uint32_t nshards, const int3
 int swimsim_group_step(swimsim_t *const *hs, uint32_t n, uint32_t nrounds, const swimsim_event *events, size_t nevents) {
     if (!hs || n < 1) return SWIMSIM_EINVAL;
     if (n == 1) return swimsim_step(hs[0], nrounds, events, nevents);
+    // every shard's checksum tables cover what any shard has admitted since the last call (agree_ecap)
+    uint32_t ecap = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        if (!hs[i]) return SWIMSIM_EINVAL;
+        ecap = std::max(ecap, hs[i]->ecap);
+    }
+    int prev = -1;
+    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+    int rc = 0;
+    for (uint32_t i = 0; i < n && !rc; i++) {
+        if (hs[i]->ecap == ecap) continue;
+        hipSetDevice(hs[i]->device);                               // (the new tables are allocated on the shard's device)
+        rc = ensure_ecap(hs[i], ecap - 1);
+    }
+    if (prev >= 0) hipSetDevice(prev);
+    if (rc) return rc;
     std::vector<int> rcs(n, 0);
     std::vector<std::thread> th;
     for (uint32_t i = 0; i < n; i++) {

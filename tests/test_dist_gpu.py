@@ -51,6 +51,13 @@ def test_three_processes(name):
     _run(3, name)
 
 
+def test_two_processes_incarnations_past_the_checksum_table():
+    """the gossip scenario of tests/incarnation_scenarios.py (n = 65, a 16-entry table): rank 0 owns every written
+    observer and grows its table at the writes; rank 1 meets the incarnations in the round's parcels only, so it has
+    to learn the table size through the transport before it hashes them"""
+    _run(2, "incarnation:make_change")
+
+
 def _bench(extra, timeout=300):
     """bench.py as the driver starts it (a child process; --gpus N > 1 starts its own torch.distributed.run)"""
     repo = os.path.dirname(HERE)

@@ -1,8 +1,9 @@
-"""Limits of the engine's representation, on the GPU (swimsim_set_member, memberlist.go:282-307 applied raw):
+"""Limits of the engine's representation, on the GPU, at every caller-facing entry point that takes an incarnation
+(swimsim_set_member, swimsim_set_row, swimsim_make_change, swimsim_add_join_list; memberlist.go:282-307 and 398-406):
 incarnations are stored as steps e of the protocol period from t0 and the checksum formatter addresses its
 record-tail table by member word ((e << 3) | status) with a 32-bit byte offset, so 2^24 steps is the limit. An
-incarnation beyond it is refused with SWIMSIM_ERANGE (never a silently wrong checksum); one just inside the
-tables already built still hashes exactly as the oracle does."""
+incarnation beyond it is refused with SWIMSIM_ERANGE (never a silently wrong checksum) and leaves the handle usable
+and unchanged; one past the tables already built, inside what they can grow to, hashes exactly as the oracle does."""
 import os
 import sys
 
@@ -34,3 +35,42 @@ def test_incarnation_beyond_checksum_tables_is_refused():
         ora.step()
         assert np.array_equal(eng.checksums(), ora.checksums())
         assert eng.digest() == ora.digest()
+
+
+def _write(sim, entry, inc):
+    """one write of incarnation inc through `entry`, on an engine or an OracleSim (they take the same calls)"""
+    if entry == "make_change":
+        return sim.make_change(3, 5, inc, swimsim.SUSPECT)
+    if entry == "set_row":
+        st = [swimsim.ALIVE] * sim.n
+        st[9] = swimsim.FAULTY
+        return sim.set_row(3, st, [swimsim.T0_MS] * 5 + [inc] * (sim.n - 5))
+    return sim.add_join_list(3, [5, 9, 11], [swimsim.ALIVE, swimsim.SUSPECT, swimsim.FAULTY],
+                             [inc, swimsim.T0_MS + PERIOD, inc], [-1, 7, -1], [0, swimsim.T0_MS, 0])
+
+
+@pytest.mark.parametrize("entry", ["make_change", "set_row", "add_join_list"])
+def test_incarnation_beyond_checksum_tables_is_refused_at_every_entry_point(entry):
+    n = 64
+    eng = swimsim.Cluster(n, device=0)
+    ora = OracleSim(n)
+    try:
+        before = eng.checksums().copy(), eng.digest()
+        with pytest.raises(swimsim.SwimsimError, match="ERANGE|2\\^24"):
+            _write(eng, entry, swimsim.T0_MS + (1 << 24) * PERIOD)
+        with pytest.raises(swimsim.SwimsimError, match="ERANGE|2\\^24"):
+            _write(eng, entry, swimsim.T0_MS + ((1 << 24) + 7) * PERIOD)
+        # the refused writes left the handle usable and unchanged
+        assert np.array_equal(eng.checksums(), before[0]) and eng.digest() == before[1]
+        assert np.array_equal(eng.checksums(), ora.checksums()) and eng.digest() == ora.digest()
+        # a large step past the tables built so far, through the same entry point: rounds still match bit for bit
+        inc = swimsim.T0_MS + ((1 << 16) + 3) * PERIOD
+        assert _write(eng, entry, inc) == _write(ora, entry, inc)
+        for _ in range(3):
+            eng.step(1)
+            ora.step()
+            assert np.array_equal(eng.checksums(), ora.checksums())
+            assert eng.digest() == ora.digest()
+            assert eng.counters() == ora.counters()
+    finally:
+        eng.close()
