@@ -326,7 +326,7 @@ struct swimsim {
     uint2 *needlist = nullptr;
     uint32_t *needcnt = nullptr, needcap = 0;
     uint32_t *hsics = nullptr, *npairs = nullptr;
-    unsigned long long *keys = nullptr, *keys_sorted = nullptr;
+    unsigned long long *keys = nullptr;
     uint32_t keycap = 0;
     uint64_t x_bytes = 0, x_calls = 0;        // exchanged bytes / exchanges (measurement)
     uint64_t x_syncs = 0;                     // host synchronisations the exchanges took (measurement)
@@ -344,10 +344,15 @@ struct swimsim {
              *dup_of = nullptr;                   // checksum dedup (rows by fingerprint)
     uint8_t *hflag = nullptr;
     uint32_t *H = nullptr, *nh = nullptr;
-    uint32_t *keys_in = nullptr, *vals_out = nullptr;    // sorted inbox: receiver column, sender-value column
-    uint4 *pinfo = nullptr;                       // per sorted inbox pair: the sender's snapshot (k_pair_info), 32 B
-    uint32_t inbox_n = 0;                         // pairs of the last sorted inbox
-    uint32_t *ukeys = nullptr, *counts = nullptr, *offs = nullptr, *nruns = nullptr, *info = nullptr;
+    // the inbox by owned row (build_inbox): per key its slot in its receiver's run; the placed sender values and their
+    // runs in arrival order; the sender values in run order; per owned row its run's size and offset (offs[NL]: total,
+    // offs[NL + 1]: rows with a message, listed in ulist)
+    uint32_t *kslot = nullptr, *vals_in = nullptr, *run_of = nullptr, *vals_out = nullptr;
+    uint4 *pinfo = nullptr;                       // per inbox pair in run order: the sender's snapshot (k_pair_info), 32 B
+    uint32_t inbox_n = 0;                         // keys of the last inbox built (sentinels included)
+    uint32_t *counts = nullptr, *offs = nullptr, *ulist = nullptr, *info = nullptr;
+    unsigned long long *scan_agg = nullptr;       // k_inbox_scan's workgroup sums, tagged with scan_gen
+    uint32_t scan_gen = 0;
     void *cub_tmp = nullptr;
     size_t cub_bytes = 0;
     uint32_t *list = nullptr, *cnt = nullptr;
@@ -673,26 +678,20 @@ int read_counters(swimsim *h, uint64_t *out /* [CTR_STRIDE] */) {
     return 0;
 }
 
-// --- sorting the (receiver << 32 | sender value) inbox keys and run-length encoding by receiver ---
-int sort_inbox(swimsim *h, uint32_t n, uint32_t *host_info) {
+// --- the (receiver << 32 | sender value) inbox keys[0, n) to one run per owned row, without a host round trip ---
+// The first nlocal keys were counted by the kernel that wrote them (k_pairs_direct, k_pairs_helpers); the keys another
+// shard sent are counted here. k_pair_info (run_waves) puts each run into sender order.
+int build_inbox(swimsim *h, uint32_t nlocal, uint32_t n) {
     Scope sc(h, F_SORT);
     h->inbox_n = n;
-    int endbit = 1;
-    while ((1u << endbit) <= h->N) endbit++;
-    size_t bytes = h->cub_bytes;
-    HIPCHK(h, hipcub::DeviceRadixSort::SortKeys(h->cub_tmp, bytes, h->keys, h->keys_sorted, (int)n, 0, 32 + endbit, h->s));
-    hipLaunchKernelGGL(k_split_keys, dim3(blocks_for_threads(n)), dim3(256), 0, h->s, h->keys_sorted, n, h->keys_in,
-                       h->vals_out);
-    bytes = h->cub_bytes;
-    HIPCHK(h, hipcub::DeviceRunLengthEncode::Encode(h->cub_tmp, bytes, h->keys_in, h->ukeys, h->counts, h->nruns,
-                                                    (int)n, h->s));
-    bytes = h->cub_bytes;
-    HIPCHK(h, hipcub::DeviceScan::ExclusiveSum(h->cub_tmp, bytes, h->counts, h->offs, (int)n, h->s));
-    HIPCHK(h, hipMemsetAsync(h->info, 0, 8, h->s));
-    hipLaunchKernelGGL(k_runs_info, dim3(blocks_for_threads(n)), dim3(256), 0, h->s, h->ukeys, h->counts, h->nruns, h->N,
-                       h->info);
-    HIPCHK(h, hipMemcpyAsync(host_info, h->info, 16, hipMemcpyDeviceToHost, h->s));
-    HIPCHK(h, stream_sync(h));
+    if (n > nlocal)
+        hipLaunchKernelGGL(k_inbox_count, dim3(blocks_for_threads(n - nlocal)), dim3(256), 0, h->s, h->d, h->keys, nlocal,
+                           n, h->counts, h->kslot);
+    h->scan_gen = h->scan_gen % 0x1FFFFFu + 1u;
+    hipLaunchKernelGGL(k_inbox_scan, dim3((h->NL + 1023) / 1024), dim3(1024), 0, h->s, h->d, h->counts, h->offs,
+                       h->ulist, h->scan_agg, h->scan_gen);
+    hipLaunchKernelGGL(k_inbox_place, dim3(blocks_for_threads(n)), dim3(256), 0, h->s, h->d, h->keys, n, h->offs,
+                       h->kslot, h->vals_in, h->run_of);
     return 0;
 }
 
@@ -961,7 +960,7 @@ int csr_hash(swimsim *h, CsrSet &c, const uint32_t *list, const uint32_t *cnt, u
         size_t bytes = cub_bytes;
         HIPCHK(h, hipcub::DeviceScan::ExclusiveSum(cub, bytes, c.Lb, c.OB, (int)h->N + 1, st));
         HIPCHK(h, hipMemsetAsync(c.SBw, 0, h->csr_sbw_words * 4, st));
-        hipLaunchKernelGGL(k_ucols, dim3(1), dim3(1024), 0, st, d);
+        hipLaunchKernelGGL(k_ucols, dim3(1), dim3(1024), 0, st, d, (uint32_t *)nullptr);
         hipLaunchKernelGGL(k_csr_ucol, dim3((h->N + 255) / 256), dim3(256), 0, st, d.ucl, d.ucnt, c.B, c.OB, c.ucol);
         launch_csr(d, list, n, cnt, ca, a, st, 0);
         launch_csr(d, list, n, cnt, ca, a, st, 1);
@@ -1166,7 +1165,7 @@ int checksum_dirty(swimsim *h, int mode, bool async = false) {
         for (int pass = 0; pass < 2; pass++)
             hipLaunchKernelGGL(k_fp_table, dim3(blocks_for_threads(n)), dim3(256), 0, h->s, h->d, h->list, n, h->fp_tab,
                                fmask, keymask, pass);
-        hipLaunchKernelGGL(k_ucols, dim3(1), dim3(1024), 0, h->s, h->d);   // (k_fp_verify_tab compares by them)
+        hipLaunchKernelGGL(k_ucols, dim3(1), dim3(1024), 0, h->s, h->d, (uint32_t *)nullptr);   // (k_fp_verify_tab compares by them)
         hipLaunchKernelGGL(k_fp_verify_tab, dim3(blocks_for_waves(n)), dim3(SWIM_WAVE_BLOCK), 0, h->s, h->d, h->list, n,
                            h->fp_tab, fmask, keymask, h->hflag, h->dup_of);
         // the rows to hash in row order (one workgroup): no sort before the hash either
@@ -1203,7 +1202,7 @@ int bound_lazy_snapshots(swimsim *h, int mode) {
     return 0;
 }
 
-// run the receive waves over a sorted inbox (phase D when phase==0, phase Q2 when phase==1), then
+// run the receive waves over a built inbox (build_inbox; phase D when phase==0, phase Q2 when phase==1), then
 // resolve the deferred full-sync decisions with one batched checksum of the receivers' snapshots
 // resolve the deferred full-sync decisions: one batched checksum of the snapshots they wait on (dirty
 // receivers, local pending senders and, when sharded, the pending senders other shards ask this
@@ -1221,8 +1220,8 @@ int resolve_deferred(swimsim *h, int phase, MsgDesc *rdesc, uint32_t maxn) {
     uint32_t maxlist = 2 * maxn;
     {
         Scope sc(h, F_CSPREP);
-        HIPCHK(h, hipMemsetAsync(h->cnt, 0, 8, h->s));
-        hipLaunchKernelGGL(k_ucols, dim3(1), dim3(1024), 0, h->s, h->d);   // (k_defer_eq compares by them)
+        // (k_defer_eq compares by the column lists; the kernel also zeroes the two list counts below)
+        hipLaunchKernelGGL(k_ucols, dim3(1), dim3(1024), 0, h->s, h->d, h->cnt);
         if (h->rep_tab) {                                          // (exits at once when nothing was deferred)
             h->rep_gen = h->rep_gen % 255u + 1u;
             hipLaunchKernelGGL(k_cs_reps, dim3(blocks_for_threads(h->NL)), dim3(256), 0, h->s, h->d, h->defer_cnt, h->rep_tab,
@@ -1248,12 +1247,11 @@ int resolve_deferred(swimsim *h, int phase, MsgDesc *rdesc, uint32_t maxn) {
         maxlist += h->keycap;
     }
     {
-        uint32_t *hc = h->hinfo + 10;
-        HIPCHK(h, hipMemcpyAsync(hc, h->cnt, 4, hipMemcpyDeviceToHost, h->s));
-        HIPCHK(h, hipMemcpyAsync(hc + 1, h->cnt + 1, 4, hipMemcpyDeviceToHost, h->s));
-        HIPCHK(h, hipMemcpyAsync(h->hinfo + 14, h->defer_cnt, 4, hipMemcpyDeviceToHost, h->s));
+        // (cnt[0..1] and defer_cnt lie side by side: one copy)
+        uint32_t *hc = h->hinfo + 13;
+        HIPCHK(h, hipMemcpyAsync(hc, h->cnt, 12, hipMemcpyDeviceToHost, h->s));
         HIPCHK(h, stream_sync(h));
-        if (phase != 2) h->round_deferred += h->hinfo[14];         // (lazy phase C's valve, checksum_dirty)
+        if (phase != 2) h->round_deferred += hc[2];                // (lazy phase C's valve, checksum_dirty)
         // the list holds main-stream snapshot slots only (k_defer_ids), so their hash needs nothing from the side
         // stream and runs beside the previous phase C's side-stream launch (both are latency-bound launches of
         // few rows); k_recv_finish then compares with side-stream checksums, so it waits for the side stream
@@ -1272,10 +1270,10 @@ int resolve_deferred(swimsim *h, int phase, MsgDesc *rdesc, uint32_t maxn) {
     return 0;
 }
 
-int run_waves(swimsim *h, int phase, uint32_t nruns_valid, uint32_t maxcount) {
+// maxpairs: a host bound on the inbox's pairs (its keys less the sentinels the host knows of)
+int run_waves(swimsim *h, int phase, uint32_t maxpairs) {
     RecvArgs a{};
-    a.ukeys = h->ukeys; a.counts = h->counts; a.offs = h->offs; a.vals = h->vals_out;
-    a.nruns_max = nruns_valid;
+    a.counts = h->counts; a.offs = h->offs; a.ulist = h->ulist;
     a.phase = phase;
     a.sdesc = phase == 0 ? h->sdesc : h->sdesc2;
     a.sI = phase == 0 ? h->sI : h->sI2;
@@ -1287,23 +1285,24 @@ int run_waves(swimsim *h, int phase, uint32_t nruns_valid, uint32_t maxcount) {
     a.fsflag = h->fsflag;
     a.r = h->round;
     a.pinfo = h->pinfo;
-    hipMemsetAsync(h->defer_cnt, 0, 4, h->s);
     {
         Scope sc(h, F_SORT);
-        // (it also empties every local row's undo log for this phase, hence at least NL threads)
+        // (it also empties every local row's undo log and the deferred decisions' count, hence at least NL threads)
         hipLaunchKernelGGL(k_pair_info, dim3(blocks_for_threads(std::max(h->inbox_n, h->NL))), dim3(256), 0, h->s, h->d,
-                           h->vals_out, h->inbox_n, phase, a.sdesc, a.sI, a.sC, a.sS, h->pinfo);
+                           h->vals_in, h->run_of, h->counts, h->offs, h->inbox_n, phase, a.sdesc, a.sI, a.sC, a.sS,
+                           h->pinfo, h->vals_out, h->defer_cnt);
     }
     {
-        Scope sc(h, F_RECV);
-        hipLaunchKernelGGL(k_recv, dim3(blocks_for_waves(nruns_valid)), dim3(SWIM_WAVE_BLOCK), 0, h->s, h->d, a);
+        Scope sc(h, F_RECV);                                         // (a wave per owned row; those past the receiving rows exit)
+        hipLaunchKernelGGL(k_recv, dim3(blocks_for_waves(h->NL)), dim3(SWIM_WAVE_BLOCK), 0, h->s, h->d, a);
     }
-    const uint32_t maxdefer = std::min<uint64_t>((uint64_t)nruns_valid * maxcount, h->d.dense_cap);
+    // (a pair defers at most once, and every deferred decision holds a dense slot)
+    const uint32_t maxdefer = std::min(maxpairs, h->d.dense_cap);
     if (int rc = resolve_deferred(h, phase, a.rdesc, maxdefer)) return rc;
     if (phase == 0) {
         Scope sc(h, F_RECVFIN);
-        hipLaunchKernelGGL(k_build_jobs, dim3(blocks_for_threads(nruns_valid)), dim3(256), 0, h->s, h->d, h->ukeys,
-                           h->counts, h->offs, h->vals_out, nruns_valid, h->fsflag);
+        hipLaunchKernelGGL(k_build_jobs, dim3(blocks_for_threads(h->NL)), dim3(256), 0, h->s, h->d, h->counts, h->offs,
+                           h->vals_out, h->fsflag);
     }
     return 0;
 }
@@ -1541,7 +1540,7 @@ int step_one(swimsim *h, const swimsim_event *ev, size_t nev, uint32_t rounds_le
         Scope sc(h, F_SELECT);
         hipMemsetAsync(h->exh_cnt, 0, 4, h->s);
         hipLaunchKernelGGL(k_select, dim3(blocks_for_threads(h->NL)), dim3(256), 0, h->s, h->d, h->tgt, h->exh_list,
-                           h->exh_cnt);
+                           h->exh_cnt, h->counts, h->info);
         hipLaunchKernelGGL(k_select_exhaust, dim3(64), dim3(64), 0, h->s, h->d, h->exh_list, h->exh_cnt, h->scratch);
     }
     // ---- I: issue (ping requests). C_o of a dirty sender is lazy (k_issue snapshots the row; it is
@@ -1549,8 +1548,8 @@ int step_one(swimsim *h, const swimsim_event *ev, size_t nev, uint32_t rounds_le
     uint32_t *hi = h->hinfo;
     uint32_t ninbox = h->NL;
     if (int rc = bound_lazy_snapshots(h, 1)) return rc;
-    HIPCHK(h, hipMemsetAsync(h->d.dense_cur, 0, 4, h->s));         // dense snapshots live from here through R
-    hot_update(h);
+    hot_update(h);                                                   // (dense snapshots live from here through R: k_select
+                                                                     // reset their cursor)
     {
         {
             Scope sc(h, F_ISSUE);
@@ -1558,9 +1557,10 @@ int step_one(swimsim *h, const swimsim_event *ev, size_t nev, uint32_t rounds_le
                                h->sdesc, h->sI, h->sC, h->sS);
         }
         Scope sc(h, F_SORT);
-        HIPCHK(h, hipMemsetAsync(h->info + 2, 0, 4, h->s));
         hipLaunchKernelGGL(k_pairs_direct, dim3(blocks_for_threads(h->NL)), dim3(256), 0, h->s, h->d, h->tgt, h->keys,
-                           h->failed, h->info, h->xitems, h->xcnt, h->xcap);
+                           h->failed, h->info, h->xitems, h->xcnt, h->xcap, h->counts, h->kslot);
+        // the failed-ping count: read after the synchronisation that resolve_deferred makes in phase D
+        HIPCHK(h, hipMemcpyAsync(&hi[2], h->info + 2, 4, hipMemcpyDeviceToHost, h->s));
     }
     if (sharded) {                                                   // requests to targets on other shards
         HIPCHK(h, hipMemcpyAsync(h->npairs, &h->NL, 4, hipMemcpyHostToDevice, h->s));
@@ -1568,15 +1568,14 @@ int step_one(swimsim *h, const swimsim_event *ev, size_t nev, uint32_t rounds_le
         HIPCHK(h, hipMemcpyAsync(&hi[5], h->npairs, 4, hipMemcpyDeviceToHost, h->s));
     }
     // ---- D: deliver in waves ----
-    // (the failed-ping count info[2] reaches the host with sort_inbox's copy of info[0..3]; a sharded inbox size
-    // needs its own round trip first)
+    // (a sharded inbox size needs a round trip of its own)
     if (sharded) {
         HIPCHK(h, stream_sync(h));
         ninbox = std::min(hi[5], h->keycap);
     }
-    if (int rc = sort_inbox(h, ninbox, hi)) return rc;
+    if (int rc = build_inbox(h, h->NL, ninbox)) return rc;
+    if (int rc = run_waves(h, 0, ninbox)) return rc;
     const uint32_t nfailed = hi[2];
-    if (int rc = run_waves(h, 0, hi[0], hi[1])) return rc;
     if (sharded) {                                                   // responses to senders on other shards
         hipLaunchKernelGGL(k_x_resp, dim3(blocks_for_threads(ninbox)), dim3(256), 0, h->s, h->d, h->keys, ninbox, 0,
                            h->xitems, h->xcnt, h->xcap);
@@ -1595,10 +1594,10 @@ int step_one(swimsim *h, const swimsim_event *ev, size_t nev, uint32_t rounds_le
         {
             Scope sc(h, F_PINGREQ);
             hipLaunchKernelGGL(k_helpers, dim3(blocks_for_threads(h->NL)), dim3(256), 0, h->s, h->d, h->tgt, h->failed,
-                               h->H, h->nh, r);
+                               h->H, h->nh, r, h->counts);
         }
+        // (dense snapshots live from here through Q3: k_helpers reset their cursor)
         if (int rc = bound_lazy_snapshots(h, 2)) return rc;
-        HIPCHK(h, hipMemsetAsync(h->d.dense_cur, 0, 4, h->s));     // dense snapshots live from here through Q3
         {
             {
                 Scope sc(h, F_ISSUE);
@@ -1607,7 +1606,7 @@ int step_one(swimsim *h, const swimsim_event *ev, size_t nev, uint32_t rounds_le
             }
             Scope sc(h, F_PINGREQ);
             hipLaunchKernelGGL(k_pairs_helpers, dim3(blocks_for_threads(h->NL * h->K)), dim3(256), 0, h->s, h->d,
-                               h->failed, h->H, h->nh, h->keys, h->xitems, h->xcnt, h->xcap);
+                               h->failed, h->H, h->nh, h->keys, h->xitems, h->xcnt, h->xcap, h->counts, h->kslot);
         }
         uint32_t ninbox2 = h->NL * h->K;
         if (sharded) {
@@ -1617,8 +1616,10 @@ int step_one(swimsim *h, const swimsim_event *ev, size_t nev, uint32_t rounds_le
             HIPCHK(h, stream_sync(h));
             ninbox2 = std::min(hi[5], h->keycap);
         }
-        if (int rc = sort_inbox(h, ninbox2, hi)) return rc;
-        if (int rc = run_waves(h, 1, hi[0], hi[1])) return rc;
+        if (int rc = build_inbox(h, h->NL * h->K, ninbox2)) return rc;
+        // (a row asks helpers only after a failed ping: at most nfailed * K local pairs beside the imported ones)
+        const uint64_t pairs2 = (uint64_t)nfailed * h->K + (ninbox2 - std::min(ninbox2, h->NL * h->K));
+        if (int rc = run_waves(h, 1, (uint32_t)std::min<uint64_t>(pairs2, ninbox2))) return rc;
         if (sharded) {
             hipLaunchKernelGGL(k_x_resp, dim3(blocks_for_threads(ninbox2)), dim3(256), 0, h->s, h->d, h->keys, ninbox2, 1,
                                h->xitems, h->xcnt, h->xcap);
@@ -1974,7 +1975,12 @@ int swimsim_create(const swimsim_config *cfg, swimsim_t **out) {
         size_t freeb = 0, totalb = 0;
         hipMemGetInfo(&freeb, &totalb);
         const uint64_t by_mem = (uint64_t)(freeb / 3) / (4ull * h->NP);
-        d.dense_cap = (uint32_t)std::max<uint64_t>(64, std::min<uint64_t>(2ull * h->NL + 64, by_mem));
+        // A shard's rows can be the targets of every member's ping (a self-only start's seed rows: N deferred
+        // decisions in one phase beside the NL lazy issue snapshots), so a shard of few rows gets N + NL slots, up to
+        // 4,096 of them; larger shards keep the two per row.
+        const uint64_t per_row = 2ull * h->NL + 64, all_pings = (uint64_t)h->N + h->NL + 64;
+        const uint64_t want_slots = std::max(per_row, std::min<uint64_t>(all_pings, 4096));
+        d.dense_cap = (uint32_t)std::max<uint64_t>(64, std::min<uint64_t>(want_slots, by_mem));
         if (tun && tun->dense_slots >= 0)                           // tests: a small pool exercises the fallbacks
             d.dense_cap = std::max<uint32_t>(64, std::min<uint32_t>(d.dense_cap, (uint32_t)tun->dense_slots));
         // side-stream checksum snapshots (latency-bound phase C launches only), up to 1/8 of the free HBM
@@ -2012,13 +2018,15 @@ int swimsim_create(const swimsim_config *cfg, swimsim_t **out) {
         (rc = dalloc(h, &h->fplist, h->NL, "fplist")) || (rc = dalloc(h, &h->fpcnt, 1, "fpcnt")) ||
         (rc = dalloc(h, &h->dup_of, h->NL, "dup_of")) || (rc = dalloc(h, &h->hflag, h->NL, "hflag")) || (rc = dalloc(h, &h->d.fp, h->NL, "fp")) ||
         (rc = dalloc(h, &h->H, NLK, "H")) || (rc = dalloc(h, &h->nh, h->NL, "nh")) ||
-        (rc = dalloc(h, &h->keys, KC, "keys")) || (rc = dalloc(h, &h->keys_sorted, KC, "keys_sorted")) ||
-        (rc = dalloc(h, &h->keys_in, KC, "receivers")) || (rc = dalloc(h, &h->vals_out, KC, "vals_out")) ||
+        (rc = dalloc(h, &h->keys, KC, "keys")) || (rc = dalloc(h, &h->kslot, KC, "inbox key slots")) ||
+        (rc = dalloc(h, &h->vals_in, KC, "vals_in")) || (rc = dalloc(h, &h->run_of, KC, "inbox runs")) ||
+        (rc = dalloc(h, &h->vals_out, KC, "vals_out")) ||
         (rc = dalloc(h, &h->pinfo, (size_t)KC * 2, "inbox pair snapshots")) ||
-        (rc = dalloc(h, &h->ukeys, KC, "ukeys")) || (rc = dalloc(h, &h->counts, KC, "counts")) ||
-        (rc = dalloc(h, &h->offs, KC, "offs")) || (rc = dalloc(h, &h->nruns, 1, "nruns")) ||
+        (rc = dalloc(h, &h->counts, h->NL, "counts")) || (rc = dalloc(h, &h->offs, (size_t)h->NL + 2, "offs")) ||
+        (rc = dalloc(h, &h->ulist, h->NL, "receiving rows")) ||
+        (rc = dalloc(h, &h->scan_agg, ((size_t)h->NL + 1023) / 1024, "inbox scan sums")) ||
         (rc = dalloc(h, &h->info, 8, "info")) || (rc = dalloc(h, &h->list, 3 * KC + 2 * (size_t)h->NL + 64, "list")) ||
-        (rc = dalloc(h, &h->cnt, 2, "cnt")) || (rc = dalloc(h, &h->defer, KC + 2 * (size_t)h->NL + 64, "defer")) ||
+        (rc = dalloc(h, &h->cnt, 3, "cnt")) || (rc = dalloc(h, &h->defer, KC + 2 * (size_t)h->NL + 64, "defer")) ||
         (rc = dalloc(h, &h->defer_eq, KC + 2 * (size_t)h->NL + 64, "defer eq")) ||
         (rc = dalloc(h, &h->rep_tab, (size_t)rep_slots(h->NL), "checksum representatives")) ||
         (rc = dalloc(h, &h->fp_tab, (size_t)rep_slots(h->NL) * 4, "dedup groups")) ||
@@ -2026,12 +2034,14 @@ int swimsim_create(const swimsim_config *cfg, swimsim_t **out) {
         (rc = dalloc(h, &h->d.ulog_cnt, (size_t)h->NL, "receive-phase undo log counts")) ||
         (rc = dalloc(h, &h->d.ilen, (size_t)h->NL, "issue-time checksum lengths")) ||
         (rc = dalloc(h, &h->d.ilast, (size_t)h->NL, "issue-time last members")) ||
-        (rc = dalloc(h, &h->defer_cnt, 1, "defer_cnt")) || (rc = dalloc(h, &h->exh_list, h->NL, "exh_list")) ||
+        (rc = dalloc(h, &h->exh_list, h->NL, "exh_list")) ||
         (rc = dalloc(h, &h->exh_cnt, 1, "exh_cnt")) || (rc = dalloc(h, &h->scratch, (size_t)64 * (h->NP / 32), "scratch")) ||
         (rc = dalloc(h, &h->need, h->N, "need")) || (rc = dalloc(h, &h->digest_buf, 4, "digest")) ||
         (rc = dalloc(h, &h->fsflag, KC, "fsflag")) || (rc = dalloc(h, &h->hsics, 4, "hsics")) ||
         (rc = dalloc(h, &h->npairs, 1, "npairs")))
         return bail(rc);
+    h->defer_cnt = h->cnt + 2;                                     // (beside the list counts: resolve_deferred's one copy)
+    hipMemset(h->scan_agg, 0, ((size_t)h->NL + 1023) / 1024 * 8);  // (generation 0: nothing published)
     h->rep_mask = (h->defer_test & 16) ? 0u : rep_slots(h->NL) - 1u;   // (tests: one slot, every checksum collides)
     h->d.ulog_stride = ULOG_STRIDE;
     h->d.ulog_cap = (h->defer_test & 8) ? 2u : ULOG_CAP;            // (tests: logs past the cap at small sizes)
@@ -2041,15 +2051,10 @@ int swimsim_create(const swimsim_config *cfg, swimsim_t **out) {
     if ((rc = dalloc(h, &h->evbuf, h->evcap, "events")) || (rc = dalloc(h, &h->ev_applied, h->evcap, "ev_applied")))
         return bail(rc);
     {
-        size_t b1 = 0, b2 = 0, b3 = 0, b4 = 0, b5 = 0;
-        hipcub::DeviceRadixSort::SortKeys(nullptr, b1, h->keys, h->keys_sorted, (int)KC, 0, 64);
-        hipcub::DeviceRunLengthEncode::Encode(nullptr, b2, h->keys_in, h->ukeys, h->counts, h->nruns, (int)KC);
-        hipcub::DeviceScan::ExclusiveSum(nullptr, b3, h->counts, h->offs, (int)KC);
-        hipcub::DeviceRadixSort::SortPairs(nullptr, b4, h->keys, h->keys_sorted, h->fpv, h->fpv_s, (int)h->NL, 0, 64);
-        hipcub::DeviceScan::InclusiveScan(nullptr, b5, h->fph, h->fph_s, hipcub::Max(), (int)h->NL);
+        // (hash_rows' sort of a row list; csr_alloc grows it for its scan)
         size_t b6 = 0;
         hipcub::DeviceRadixSort::SortKeys(nullptr, b6, h->fplist, h->list, (int)h->NL, 0, 32);
-        h->cub_bytes = std::max(std::max(std::max(b1, b6), std::max(b2, b3)), std::max(b4, b5));
+        h->cub_bytes = b6;
         if ((rc = dalloc(h, (uint8_t **)&h->cub_tmp, h->cub_bytes, "cub temp"))) return bail(rc);
     }
     // single shard until swimsim_comm_attach / swimsim_group_create says otherwise

@@ -1220,9 +1220,13 @@ __global__ void k_timers(DS d, uint32_t round) {
 // ---------------------------------------------------------------------------------------------
 // phase S: memberlistIter.Next (memberlist_iter.go:50-72) on Philox permutations
 // ---------------------------------------------------------------------------------------------
-__global__ void k_select(DS d, int32_t *tgt, uint32_t *exh_list, uint32_t *exh_cnt) {
+// It also starts the round's direct-ping phase: every owned row's inbox count, the failed-ping count info[2] and the
+// dense snapshot cursor (snapshots live from k_issue through R) are zero before k_issue and k_pairs_direct run.
+__global__ void k_select(DS d, int32_t *tgt, uint32_t *exh_list, uint32_t *exh_cnt, uint32_t *counts, uint32_t *info) {
     const uint32_t ol = blockIdx.x * blockDim.x + threadIdx.x;
+    if (ol == 0) { info[2] = 0u; *d.dense_cur = 0u; }
     if (ol >= d.NL) return;
+    counts[ol] = 0u;
     const uint32_t o = d.lo + ol;
     int32_t target = -1;
     if (d.live[o]) {
@@ -1365,10 +1369,19 @@ __global__ void k_issue(DS d, int mode, const int32_t *tgt, const uint8_t *faile
 }
 
 // ---------------------------------------------------------------------------------------------
-// phase D / Q2 inbox construction (sorted by receiver; ascending sender inside a receiver)
+// phase D / Q2 inbox construction (one run per owned row; ascending sender value inside a run)
 // ---------------------------------------------------------------------------------------------
-// inbox keys are (receiver << 32 | sender value): sorting them orders every receiver's inbox by sender,
-// wherever the pair came from (local or imported from another shard)
+// inbox keys are (receiver << 32 | sender value), local or imported from another shard. Receivers are owned rows, so
+// the inbox is built by counting: a key takes the next slot of its receiver's run (inbox_count), one workgroup scans
+// the run sizes (k_inbox_scan), every sender value goes to its run in arrival order (k_inbox_place), and k_pair_info
+// ranks it among its run's values. Sender values are distinct, so the ranks are the ascending order whatever the
+// arrival order was.
+__device__ __forceinline__ void inbox_count(const DS &d, unsigned long long key, uint32_t *counts, uint32_t *kslot,
+                                            uint32_t i) {
+    const uint32_t u = (uint32_t)(key >> 32) - d.lo;              // (the sentinel receiver N is no owned row)
+    if (u < d.NL) kslot[i] = atomicAdd(&counts[u], 1u);
+}
+
 __device__ __forceinline__ void x_push(uint4 *items, uint32_t *cnt, uint32_t cap, uint32_t *err, uint4 it) {
     const uint32_t i = atomicAdd(cnt, 1u);
     if (i < cap) items[i] = it;
@@ -1376,7 +1389,7 @@ __device__ __forceinline__ void x_push(uint4 *items, uint32_t *cnt, uint32_t cap
 }
 
 __global__ void k_pairs_direct(DS d, const int32_t *tgt, unsigned long long *keys, uint8_t *failed, uint32_t *info,
-                               uint4 *xitems, uint32_t *xcnt, uint32_t xcap) {
+                               uint4 *xitems, uint32_t *xcnt, uint32_t xcap, uint32_t *counts, uint32_t *kslot) {
     const uint32_t ol = blockIdx.x * blockDim.x + threadIdx.x;
     if (ol >= d.NL) return;
     const uint32_t o = d.lo + ol;
@@ -1395,12 +1408,17 @@ __global__ void k_pairs_direct(DS d, const int32_t *tgt, unsigned long long *key
     }
     keys[ol] = key;
     failed[ol] = f;
+    inbox_count(d, key, counts, kslot, ol);
 }
 
-// RandomPingableMembers(k, {target}) (memberlist.go:201-219) with the Philox draw rule
-__global__ void k_helpers(DS d, const int32_t *tgt, const uint8_t *failed, uint32_t *H, uint32_t *nh, uint32_t r) {
+// RandomPingableMembers(k, {target}) (memberlist.go:201-219) with the Philox draw rule. It also starts the ping-req
+// phase: the rows' inbox counts and the dense snapshot cursor (snapshots live from the second k_issue through Q3)
+__global__ void k_helpers(DS d, const int32_t *tgt, const uint8_t *failed, uint32_t *H, uint32_t *nh, uint32_t r,
+                          uint32_t *counts) {
     const uint32_t ol = blockIdx.x * blockDim.x + threadIdx.x;
+    if (ol == 0) *d.dense_cur = 0u;
     if (ol >= d.NL) return;
+    counts[ol] = 0u;
     nh[ol] = 0;
     if (!failed[ol]) return;
     const uint32_t o = d.lo + ol, t = (uint32_t)tgt[ol], K = d.K;
@@ -1434,7 +1452,8 @@ __global__ void k_helpers(DS d, const int32_t *tgt, const uint8_t *failed, uint3
 }
 
 __global__ void k_pairs_helpers(DS d, const uint8_t *failed, const uint32_t *H, const uint32_t *nh,
-                                unsigned long long *keys, uint4 *xitems, uint32_t *xcnt, uint32_t xcap) {
+                                unsigned long long *keys, uint4 *xitems, uint32_t *xcnt, uint32_t xcap, uint32_t *counts,
+                                uint32_t *kslot) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     const uint32_t K = d.K;
     if (i >= d.NL * K) return;
@@ -1450,25 +1469,79 @@ __global__ void k_pairs_helpers(DS d, const uint8_t *failed, const uint32_t *H, 
         }
     }
     keys[i] = key;
+    inbox_count(d, key, counts, kslot, i);
 }
 
-// sorted 64-bit inbox keys → receiver column (run-length encoded next) and sender-value column
-__global__ void k_split_keys(const unsigned long long *keys, uint32_t n, uint32_t *recv, uint32_t *vals) {
+// the keys another shard sent (k_x_unpack appended them behind the local ones): keys[first, n)
+__global__ void k_inbox_count(DS d, const unsigned long long *keys, uint32_t first, uint32_t n, uint32_t *counts,
+                              uint32_t *kslot) {
+    const uint32_t i = first + blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) inbox_count(d, keys[i], counts, kslot, i);
+}
+
+// offs[u] = counts[0] + … + counts[u - 1] for the NL owned rows, offs[NL] = the inbox's size, and the rows with a
+// message in ascending order in ulist[0, offs[NL + 1]) (k_recv gives its first waves to them: every resident wave then
+// has a receiver), in one launch. Both sums ride in one 64-bit word (low: messages, high: rows with one). A workgroup
+// scans its 1,024 counts (a wave scan, the 16 wave totals through LDS), publishes their sum as agg[workgroup] =
+// gen << 43 | sum, and its first wave adds up the sums of the workgroups before it, waiting for each. gen is the host's
+// count of these launches in [1, 2^21): every launch overwrites every word, so a word not yet written holds the launch
+// before's gen (or 0, the array's first content) and agg is never cleared. Workgroups start in index order and wait
+// only for earlier ones, so the wait ends however many are resident.
+__global__ void __launch_bounds__(1024) k_inbox_scan(DS d, const uint32_t *counts, uint32_t *offs, uint32_t *ulist,
+                                                     unsigned long long *agg, uint32_t gen) {
+    __shared__ unsigned long long wsum[16];
+    __shared__ unsigned long long prior;
+    const uint32_t t = threadIdx.x, lane = t & 63u, w = t >> 6, b = blockIdx.x;
+    const uint32_t i = b * 1024u + t, c = i < d.NL ? counts[i] : 0u;
+    const unsigned long long v = (unsigned long long)c | ((unsigned long long)(c != 0u) << 32);
+    unsigned long long x = v;                                      // inclusive scan over the wave
+    for (uint32_t o = 1; o < 64; o <<= 1) {
+        const unsigned long long y = __shfl_up(x, o);
+        if (lane >= o) x += y;
+    }
+    if (lane == 63) wsum[w] = x;
+    __syncthreads();
+    unsigned long long before = 0, all = 0;
+    for (uint32_t k = 0; k < 16; k++) {
+        const unsigned long long s = wsum[k];
+        before += k < w ? s : 0ull;
+        all += s;
+    }
+    if (t == 0)                                                    // (all's high half is at most 1,024: 11 bits)
+        __hip_atomic_store(&agg[b], ((unsigned long long)gen << 43) | all, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (w == 0) {
+        unsigned long long s = 0;
+        for (uint32_t k = lane; k < b; k += 64) {
+            unsigned long long a;
+            while ((uint32_t)((a = __hip_atomic_load(&agg[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) >> 43) != gen)
+                __builtin_amdgcn_s_sleep(1);
+            s += a & ((1ull << 43) - 1ull);
+        }
+        for (uint32_t o = 32; o; o >>= 1) s += __shfl_xor(s, o);
+        if (lane == 0) prior = s;
+    }
+    __syncthreads();
+    const unsigned long long at = prior + before + x - v;
+    if (i < d.NL) offs[i] = (uint32_t)at;
+    if (c) ulist[(uint32_t)(at >> 32)] = i;
+    if (i + 1 == d.NL) {
+        offs[d.NL] = (uint32_t)(at + v);
+        offs[d.NL + 1] = (uint32_t)((at + v) >> 32);
+    }
+}
+
+// every sender value to its receiver's run, at the slot its key took when it was counted (arrival order), with the
+// run's row beside it for k_pair_info
+__global__ void k_inbox_place(DS d, const unsigned long long *keys, uint32_t n, const uint32_t *offs,
+                              const uint32_t *kslot, uint32_t *vals_in, uint32_t *run_of) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const unsigned long long k = keys[i];
-    recv[i] = (uint32_t)(k >> 32);
-    vals[i] = (uint32_t)k;
-}
-
-// runs: number of receivers (excluding the sentinel) and the longest inbox
-__global__ void k_runs_info(const uint32_t *ukeys, const uint32_t *counts, const uint32_t *nruns, uint32_t N,
-                            uint32_t *info) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= *nruns) return;
-    if (ukeys[i] == N) return;
-    atomicMax(&info[1], counts[i]);
-    atomicAdd(&info[0], 1u);
+    const uint32_t u = (uint32_t)(k >> 32) - d.lo;
+    if (u >= d.NL) return;
+    const uint32_t p = offs[u] + kslot[i];
+    vals_in[p] = (uint32_t)k;
+    run_of[p] = u;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1476,10 +1549,10 @@ __global__ void k_runs_info(const uint32_t *ukeys, const uint32_t *counts, const
 // (ping_handler.go:25-58 / ping_request_handler.go:32-76)
 // ---------------------------------------------------------------------------------------------
 struct RecvArgs {
-    const uint32_t *ukeys, *counts, *offs, *vals;   // run-length encoded sorted inbox
+    const uint32_t *counts, *offs;                  // the inbox by owned row: run u is receiver lo + u
+    const uint32_t *ulist;                          // the rows with a message, ascending: offs[NL + 1] of them
     const uint4 *pinfo;                             // per inbox pair (k_pair_info): {sender's message descriptor},
                                                     // {I_o, C_o, lazy slot, sender value}
-    uint32_t nruns_max;
     int phase;                                      // 0: direct ping (phase D), 1: ping-req (Q2)
     const MsgDesc *sdesc;                           // sender snapshots (by global sender id)
     const uint32_t *sI, *sC;
@@ -1493,21 +1566,53 @@ struct RecvArgs {
     uint32_t r;
 };
 
-// the inbox pairs' sender snapshots in pair order (one thread per pair, after the inbox sort): a receiver's wave then
+// the inbox pairs' sender snapshots in pair order (one thread per pair, after k_inbox_place): a receiver's wave then
 // reads its message's descriptor and the sender's I_o, C_o and lazy slot with one load that depends only on its run's
 // offset, instead of the pair's sender value and then four arrays indexed by it (two dependent round trips)
-__global__ void k_pair_info(const DS d, const uint32_t *vals, uint32_t n, int phase, const MsgDesc *sdesc, const uint32_t *sI,
-                            const uint32_t *sC, const uint32_t *sS, uint4 *pinfo) {
+// The thread of placed element i also orders its run: the element's rank is the number of its run's values below its
+// own, and the pair's words and its sender value (vals_out) go to the run's offset + rank. A run of at most 64 values is
+// counted by each lane for itself (lanes of one run read the same word). Longer runs (a seed's inbox in a self-only
+// start holds N/2 messages) are taken one at a time by the whole wave: 64 of the run's values per load, each passed to
+// every lane from a register, so the cost is two instructions per value and no lane waits on memory per value.
+constexpr uint32_t RANK_LANE_MAX = 64;
+__global__ void k_pair_info(const DS d, const uint32_t *vals_in, const uint32_t *run_of, const uint32_t *counts,
+                            const uint32_t *offs, uint32_t n, int phase, const MsgDesc *sdesc, const uint32_t *sI,
+                            const uint32_t *sC, const uint32_t *sS, uint4 *pinfo, uint32_t *vals_out, uint32_t *defer_cnt) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     // the phase's undo logs start empty, also those of the rows that will receive nothing (k_defer_eq reads a sender's
-    // count whether or not it was a receiver); the grid covers max(n, NL) threads
+    // count whether or not it was a receiver); the grid covers max(n, NL) threads. The deferred decisions' count too.
     if (d.ulog_cnt && i < d.NL) d.ulog_cnt[i] = 0u;
-    if (i >= n) return;
-    const uint32_t v = vals[i], sender = phase == 0 ? v : v / d.K;
-    if (sender >= d.N) return;                                     // (sentinel keys: no receiver reads them)
+    if (i == 0) *defer_cnt = 0u;
+    const bool valid = i < min(n, offs[d.NL]);                     // (whole waves stay for the long runs' loop)
+    uint32_t v = 0, off = 0, c = 0, rank = 0;
+    if (valid) {
+        const uint32_t u = run_of[i];
+        v = vals_in[i]; off = offs[u]; c = counts[u];
+    }
+    if (c > 1 && c <= RANK_LANE_MAX)
+        for (uint32_t k = 0; k < c; k++) rank += vals_in[off + k] < v;
+    unsigned long long todo = __ballot(c > RANK_LANE_MAX);
+    while (todo) {
+        const int l = __builtin_ctzll(todo);
+        const uint32_t off_u = (uint32_t)__shfl((int)off, l), c_u = (uint32_t)__shfl((int)c, l);
+        const bool mine = c > RANK_LANE_MAX && off == off_u;
+        uint32_t rk = 0;
+        for (uint32_t base = 0; base < c_u; base += 64) {
+            const uint32_t at = base + lane_id();
+            const uint32_t x = at < c_u ? vals_in[off_u + at] : 0xFFFFFFFFu;   // (no value is below no sender value)
+#pragma unroll
+            for (int k = 0; k < 64; k++) rk += (uint32_t)__builtin_amdgcn_readlane((int)x, k) < v;
+        }
+        if (mine) rank = rk;
+        todo &= ~__ballot(mine);
+    }
+    if (!valid) return;
+    const uint32_t p = off + rank, sender = phase == 0 ? v : v / d.K;
+    vals_out[p] = v;
+    if (sender >= d.N) return;
     const MsgDesc md = sdesc[sender];
-    pinfo[2 * (size_t)i] = make_uint4(md.off_lo, md.off_hi, md.len, md.kind);
-    pinfo[2 * (size_t)i + 1] = make_uint4(sI[sender], sC[sender], sS ? sS[sender] : SRC_NONE, v);
+    pinfo[2 * (size_t)p] = make_uint4(md.off_lo, md.off_hi, md.len, md.kind);
+    pinfo[2 * (size_t)p + 1] = make_uint4(sI[sender], sC[sender], sS ? sS[sender] : SRC_NONE, v);
 }
 
 // the full-sync branch of IssueAsReceiver (disseminator.go:161-180): taken iff the filtered list is
@@ -1593,11 +1698,11 @@ __device__ __forceinline__ void recv_one_pre(const DS &d, const RecvArgs &a, uin
 // so resident waves, not registers, set the pace
 constexpr int RECV_MIN_WAVES = 4;
 __global__ void __launch_bounds__(256, RECV_MIN_WAVES) k_recv(DS d, RecvArgs a) {
-    const uint32_t u = wave_gid();
-    if (u >= a.nruns_max) return;
-    const uint32_t key = a.ukeys[u];
-    if (key >= d.N) return;
-    const uint32_t n = a.counts[u], off = a.offs[u];
+    const uint32_t w = wave_gid();
+    if (w >= d.NL) return;
+    const uint32_t u = a.ulist[w];                                  // (read beside the count; stale past it, never used)
+    if (w >= a.offs[d.NL + 1]) return;
+    const uint32_t n = a.counts[u], off = a.offs[u], key = d.lo + u;
     RowPre p = row_pre(d, key - d.lo);
     const uint32_t now = wave_clock(d, key, a.r);                  // the receiver's clock: refutes, timer schedules
     const uint32_t nslots = d.hidx ? d.hot_cnt[0] : 0u;
@@ -1631,11 +1736,13 @@ __global__ void k_colx_rebuild(DS d) {
 
 // the divergent-column lists (DS::ucl / uhk / ucold / ucnt) from the bitmap (one workgroup of 1024 threads: each thread
 // a run of bitmap words, a block prefix sum of their bit counts)
-__global__ void __launch_bounds__(1024) k_ucols(DS d) {
+// zero2: two counter words that the caller's next kernels count into (resolve_deferred's list sizes), or null
+__global__ void __launch_bounds__(1024) k_ucols(DS d, uint32_t *zero2) {
     __shared__ uint32_t part[1024];
     __shared__ uint32_t ncold;
     const uint32_t t = threadIdx.x, per = (d.NBIT + 1023) / 1024, w0 = t * per;
     if (t == 0) ncold = 0;
+    if (t == 0 && zero2) zero2[0] = zero2[1] = 0u;
     auto bitsof = [&](uint32_t w) -> uint32_t {                    // (bits of members >= N masked off)
         const uint32_t x = d.colx[w], lo = w * 32;
         return lo + 32 <= d.N ? x : lo >= d.N ? 0u : x & ((1u << (d.N - lo)) - 1u);
@@ -1956,11 +2063,10 @@ __global__ void k_defer_ids(DS d, const uint4 *defer, const uint32_t *defer_cnt,
 }
 
 // tryStartReverseFullSync (disseminator.go:257-278) in inbox order: at most maxjobs per receiver
-__global__ void k_build_jobs(DS d, const uint32_t *ukeys, const uint32_t *counts, const uint32_t *offs,
-                             const uint32_t *vals, uint32_t nruns, uint8_t *fsflag) {
-    const uint32_t u = blockIdx.x * blockDim.x + threadIdx.x;
-    if (u >= nruns || ukeys[u] >= d.N) return;
-    const uint32_t ol = ukeys[u] - d.lo;
+__global__ void k_build_jobs(DS d, const uint32_t *counts, const uint32_t *offs, const uint32_t *vals,
+                             uint8_t *fsflag) {
+    const uint32_t u = blockIdx.x * blockDim.x + threadIdx.x, ol = u;
+    if (u >= d.NL) return;
     for (uint32_t w = 0; w < counts[u]; w++) {
         const uint32_t p = offs[u] + w;
         if (!fsflag[p]) continue;
