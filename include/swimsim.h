@@ -28,7 +28,8 @@
 extern "C" {
 #endif
 
-#define SWIMSIM_ABI_VERSION 12   /* 12: the checksum block-stream dump call is gone (only a diagnostics build ever
+#define SWIMSIM_ABI_VERSION 13   /* 13: swimsim_pool_usage (a read-back; nothing else changed since 12). 12: the
+                                    checksum block-stream dump call is gone (only a diagnostics build ever
                                     implemented it, and that build is gone); nothing else changed since 11 */
 
 enum {
@@ -205,7 +206,14 @@ int swimsim_clock_offsets(swimsim_t *h, int64_t *out);
 
 /* ---- the hot path: nrounds protocol periods of every live node (gossip.ProtocolPeriod,
  *      gossip.go:178-188, for all N nodes under docs/ROUND_SEMANTICS.md). events are applied
- *      in phase E of the round equal to their .round field. ---- */
+ *      in phase E of the round equal to their .round field.
+ *      SWIMSIM_ECAPACITY (a device pool overflowed: swimsim_last_error names it) is detected once, after the last
+ *      round of the call: the round whose allocation failed went on with empty messages in place of the ones that
+ *      did not fit, and the call's later rounds ran on top of it. The handle's protocol state is then unspecified
+ *      (no read-back of it is meaningful, and swimsim_round counts every round of the call); every access stayed
+ *      inside the handle's buffers, the error word is cleared, and the process and its other handles are unaffected.
+ *      Destroy the handle and create one with larger pools (swimsim_config.message_pool_bytes). A caller that must
+ *      know the last good round steps one round per call. The same holds for swimsim_heal and swimsim_group_step. ---- */
 int swimsim_step(swimsim_t *h, uint32_t nrounds, const swimsim_event *events, size_t nevents);
 /* Heal() on one observer right now (heal_via_discover_provider.go:120-177); targets may be NULL */
 int swimsim_heal(swimsim_t *h, uint32_t observer, int32_t *targets, size_t cap, size_t *ntargets);
@@ -297,6 +305,12 @@ typedef struct swimsim_memory_t {
     uint64_t lazy_fallbacks;
 } swimsim_memory_t;
 int swimsim_memory(swimsim_t *h, swimsim_memory_t *out);
+/* the message pool's fill (ABI 13; a copy of 64 words, no launch): the pool is 64 sub-pools of *sub_records change
+ * records each, and cursors[s] is the number of records taken from sub-pool s since the cursors were last reset,
+ * which is at the start of every round and of swimsim_heal: after swimsim_step(h, 1, ...) they describe that round,
+ * early response reservations included. A cursor above *sub_records: an allocation of at most sub_records / 256
+ * records did not fit there and moved on to the next sub-pool (the sub-pool is full). All 0 before the first round. */
+int swimsim_pool_usage(swimsim_t *h, uint64_t *sub_records, uint64_t *cursors /* [64] */);
 
 /* ---- member census (ABI 8): how the cluster sees each member ----
  * No reference counterpart: these stand in for polling NodeInterface.MemberStats (stats.go:41-52) on every node and

@@ -1969,6 +1969,8 @@ int swimsim_create(const swimsim_config *cfg, swimsim_t **out) {
     d.pool_cap = want_records;
     if ((rc = dalloc(h, &d.pool, want_records, "message pool")) || (rc = dalloc(h, &d.pool_cur, POOL_SHARDS * POOL_CUR_STRIDE, "pool cursors")))
         return bail(rc);
+    // (a round resets the cursors before it allocates; swimsim_pool_usage may read them before the first round)
+    if (hipMemset(d.pool_cur, 0, POOL_SHARDS * POOL_CUR_STRIDE * 8) != hipSuccess) return bail(SWIMSIM_EHIP);
     {
         // dense snapshots (full-sync payloads, deferred full-sync decisions, reverse-full-sync sources):
         // up to 2 per observer row, bounded by a third of the free HBM
@@ -2859,6 +2861,17 @@ int swimsim_memory(swimsim_t *h, swimsim_memory_t *out) {
     out->dense_cap = h->d.dense_cap;
     out->side_cap = h->snap_cap;
     out->lazy_fallbacks = h->lazy_fallbacks;
+    return SWIMSIM_OK;
+}
+
+// the message pool's sub-pool cursors as the last round (or swimsim_heal) left them: a copy, no launch
+int swimsim_pool_usage(swimsim_t *h, uint64_t *sub_records, uint64_t *cursors) {
+    if (!h || !sub_records || !cursors) return SWIMSIM_EINVAL;
+    std::vector<unsigned long long> cur((size_t)POOL_SHARDS * POOL_CUR_STRIDE);
+    HIPCHK(h, hipMemcpyAsync(cur.data(), h->d.pool_cur, cur.size() * 8, hipMemcpyDeviceToHost, h->s));
+    HIPCHK(h, stream_sync(h));
+    *sub_records = h->d.pool_cap / POOL_SHARDS;
+    for (uint32_t s = 0; s < POOL_SHARDS; s++) cursors[s] = cur[(size_t)s * POOL_CUR_STRIDE];
     return SWIMSIM_OK;
 }
 

@@ -2413,8 +2413,11 @@ __global__ void k_heal_diff(DS d, const MsgDesc *ma, const MsgDesc *mb, MsgDesc 
         pb += __popcll(mb_);
     }
     if (lane_id() == 0) {
-        outA->kind = 0; outA->len = (uint32_t)na; outA->off_lo = (uint32_t)oa; outA->off_hi = (uint32_t)(oa >> 32);
-        outB->kind = 0; outB->len = (uint32_t)nb; outB->off_lo = (uint32_t)ob; outB->off_hi = (uint32_t)(ob >> 32);
+        // (a failed allocation leaves an empty message, as wave_issue_t does: E_POOL is set, and no reader of the
+        // descriptor may follow an offset of ~0)
+        const bool fa = oa == ~0ull, fb = ob == ~0ull;
+        outA->kind = 0; outA->len = fa ? 0u : (uint32_t)na; outA->off_lo = fa ? 0u : (uint32_t)oa; outA->off_hi = fa ? 0u : (uint32_t)(oa >> 32);
+        outB->kind = 0; outB->len = fb ? 0u : (uint32_t)nb; outB->off_lo = fb ? 0u : (uint32_t)ob; outB->off_hi = fb ? 0u : (uint32_t)(ob >> 32);
     }
 }
 

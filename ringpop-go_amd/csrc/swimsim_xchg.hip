@@ -161,10 +161,12 @@ __global__ void k_x_unpack(DS d, XArgs x, const uint8_t *buf, const ulonglong2 *
     MsgDesc md;
     md.kind = h.kind; md.len = h.len; md.off_lo = md.off_hi = 0;
     if (h.kind == 0 && h.len) {                                    // change records → local pool
+        // (the pool is full, E_POOL is set: the parcel is imported as an empty message, so that its descriptor is
+        // written like any other; one left as it was could be one that no round has written yet)
         const unsigned long long off = pool_alloc(d, h.len);
-        if (off == ~0ull) return;
+        if (off == ~0ull) md.len = 0;
         // (re-tagged with this shard's hot slots: the sender's tags name the sender shard's slots, DS record format)
-        for (uint32_t i = lane_id(); i < h.len; i += 64 * SNAP_MB) {
+        for (uint32_t i = lane_id(); i < md.len; i += 64 * SNAP_MB) {
             uint4 v[SNAP_MB];
             uint32_t hk[SNAP_MB];
 #pragma unroll
@@ -175,25 +177,29 @@ __global__ void k_x_unpack(DS d, XArgs x, const uint8_t *buf, const ulonglong2 *
             for (int u = 0; u < SNAP_MB; u++)
                 if (i + 64u * u < h.len) d.pool[off + i + 64u * u] = rec_retag(v[u], tag_of_slot(hk[u]));
         }
-        md.off_lo = (uint32_t)off;
-        md.off_hi = (uint32_t)(off >> 32);
+        if (md.len) {
+            md.off_lo = (uint32_t)off;
+            md.off_hi = (uint32_t)(off >> 32);
+        }
     } else if (h.kind == 1) {                                      // dense snapshot → local dense pool
         uint32_t slot = 0;
         if (lane_id() == 0) slot = atomicAdd(d.dense_cur, 1u);
         slot = (uint32_t)__shfl((int)slot, 0, 64);
         if (slot >= d.dense_cap) {
+            // (no slot, E_DENSE is set: the descriptor is written as wave_snapshot leaves one it could not fill)
             if (lane_id() == 0) atomicOr(d.err, E_DENSE);
-            return;
+            md.kind = 2; md.len = 0;
+        } else {
+            uint4 *dst = (uint4 *)(d.dense + (size_t)slot * d.NP);
+            wave_copy16(dst, payload, d.NP / 4);
+            if (lane_id() == 0) {
+                d.dense_meta[slot] = make_uint4(h.meta.x, h.meta.y, h.meta.z, 0u);   // w: a local alias only
+                d.dense_len[slot] = h.dlen;
+                d.dense_last[slot] = h.dlast;
+                d.dense_cs[slot] = h.dcs;
+            }
+            md.off_lo = slot;
         }
-        uint4 *dst = (uint4 *)(d.dense + (size_t)slot * d.NP);
-        wave_copy16(dst, payload, d.NP / 4);
-        if (lane_id() == 0) {
-            d.dense_meta[slot] = make_uint4(h.meta.x, h.meta.y, h.meta.z, 0u);   // w: a local alias only
-            d.dense_len[slot] = h.dlen;
-            d.dense_last[slot] = h.dlast;
-            d.dense_cs[slot] = h.dcs;
-        }
-        md.off_lo = slot;
     }
     __threadfence_block();
     if (lane_id() != 0) return;

@@ -184,6 +184,7 @@ def load_library(path: str = LIB_PATH):
                                              C.POINTER(u32), C.POINTER(u32), C.POINTER(i32)]),
         "swimsim_protocol_stats": (C.c_int, [P, C.POINTER(ProtocolStatsC)]),
         "swimsim_memory": (C.c_int, [P, C.POINTER(MemoryC)]),
+        "swimsim_pool_usage": (C.c_int, [P, _U64P, _U64P]),
         "swimsim_census": (C.c_int, [P, P, sz, i32, P, P, P, C.POINTER(C.c_double)]),
         "swimsim_trace_members": (C.c_int, [P, P, sz, u32]),
         "swimsim_trace_read": (C.c_int, [P, P, P, P, sz, C.POINTER(sz), C.POINTER(u32)]),
@@ -464,6 +465,15 @@ class Cluster:
         m = MemoryC()
         self._chk(load_library().swimsim_memory(self.h, C.byref(m)))
         return {f: getattr(m, f) for f, _ in MemoryC._fields_}
+
+    def pool_usage(self):
+        """(records per sub-pool, the 64 sub-pool cursors as uint64) of the message pool (swimsim_pool_usage): after
+        step(1) the records that round took from each sub-pool; a cursor above the sub-pool's size marks a small
+        allocation that overflowed there and moved on"""
+        sub = C.c_uint64()
+        cur = np.zeros(64, np.uint64)
+        self._chk(load_library().swimsim_pool_usage(self.h, C.byref(sub), cur.ctypes.data_as(_U64P)))
+        return int(sub.value), cur
 
     def protocol_stats(self):
         """NodeInterface.ProtocolStats (stats.go:81-104): Timing over protocol rounds (ns), ProtocolRate (ns),
@@ -1038,6 +1048,10 @@ class ShardedCluster:
 
     def shard_info(self):
         return [c.shard_info() for c in self.shards]
+
+    def pool_usage(self):
+        """Cluster.pool_usage() of every shard: each shard has a message pool of its own"""
+        return [c.pool_usage() for c in self.shards]
 
     # setup calls act on the owning shard (row writes) or on every shard (topology)
     def set_member(self, o, m, status, inc):

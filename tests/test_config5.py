@@ -95,5 +95,8 @@ def test_message_pool_must_hold_the_longest_message_per_sub_pool():
     with pytest.raises(swimsim.SwimsimError):
         swimsim.Cluster(n, message_pool_bytes=64 * n * 16 - 16)
     eng = swimsim.Cluster(n, message_pool_bytes=64 * n * 16)
+    sub, cur = eng.pool_usage()
+    assert sub == n and cur.shape == (64,) and not cur.any()       # (no round yet)
     eng.step(3)
+    assert not eng.pool_usage()[1].any()                            # idle rounds allocate nothing: tests/test_pool.py fills it
     eng.close()
