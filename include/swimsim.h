@@ -258,7 +258,9 @@ int swimsim_converged(swimsim_t *h, int32_t *out);
  * the checksum at the previous drain (OldChecksum), the current one (NewChecksum) and NumMembers. n = 0:
  * nothing applied, no event. Evictions are not events (RemoveMember emits none, memberlist.go:141-162).
  * At most 64 watched observers per handle.
- * on = 1: the coalesced drain below. on = 2: also the per-Update stream (swimsim_applied_events). on = 0: off. */
+ * on = 1: the coalesced drain below. on = 2: also the per-Update stream (swimsim_applied_events). on = 0: off (the
+ * observer's slot is free again and what its logs still held is dropped). Any other value of on is refused with
+ * SWIMSIM_EINVAL before anything is allocated or changed. */
 int swimsim_watch(swimsim_t *h, uint32_t observer, int32_t on);
 int swimsim_applied_changes(swimsim_t *h, uint32_t observer, int32_t *member, int32_t *status, int64_t *inc_ms,
                             int32_t *source, int64_t *source_inc_ms, size_t cap, size_t *n, uint32_t *old_checksum,
@@ -272,7 +274,10 @@ int swimsim_applied_changes(swimsim_t *h, uint32_t observer, int32_t *member, in
  * OldChecksum / NewChecksum / NumMembers are per DRAIN, not per event: the checksum at the previous drain of this
  * stream, the current checksum and the current member count (the reference computes one checksum per Update,
  * memberlist.go:367; this engine keeps the per-round ones). *n = total changes (also when > cap: only cap are
- * written). SWIMSIM_ECAPACITY: more than 4*N changes since the last drain (the stream restarts empty). */
+ * written). The log of one observer holds the larger of 4,096 and 4 x N' changes since its last drain, N' = N rounded
+ * up to a multiple of 64 (4,096 changes up to N = 1,024). SWIMSIM_ECAPACITY: more changes than that were applied since
+ * the last drain; nothing is written, the stream restarts empty and the next drain's OldChecksum is the checksum at
+ * the refused one. The coalesced drain of the same observer is not affected. */
 int swimsim_applied_events(swimsim_t *h, uint32_t observer, int32_t *member, int32_t *status, int64_t *inc_ms,
                            int32_t *source, int64_t *source_inc_ms, uint32_t *event, size_t cap, size_t *n,
                            size_t *nevents, uint32_t *old_checksum, uint32_t *new_checksum, int32_t *num_members);

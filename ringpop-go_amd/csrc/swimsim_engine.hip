@@ -2633,6 +2633,7 @@ int swimsim_profile_mark(swimsim_t *h, uint32_t id) {
 // ---- applied-change stream: MemberlistChangesAppliedEvent (swim/events.go:56-61) ----
 int swimsim_watch(swimsim_t *h, uint32_t o, int32_t on) {
     if (!h || !own(h, o)) return SWIMSIM_EINVAL;
+    if (on < 0 || on > 2) return h->fail(SWIMSIM_EINVAL, "swimsim_watch: on is 0, 1 or 2, not %d", on);
     const uint32_t ol = o - h->lo;
     if (!h->d.wslot) {
         if (!on) return SWIMSIM_OK;
