@@ -28,7 +28,8 @@
 extern "C" {
 #endif
 
-#define SWIMSIM_ABI_VERSION 13   /* 13: swimsim_pool_usage (a read-back; nothing else changed since 12). 12: the
+#define SWIMSIM_ABI_VERSION 14   /* 14: swimsim_tuning.resp_echo and the unit "resp_echoed" (results unchanged).
+                                    13: swimsim_pool_usage (a read-back; nothing else changed since 12). 12: the
                                     checksum block-stream dump call is gone (only a diagnostics build ever
                                     implemented it, and that build is gone); nothing else changed since 11 */
 
@@ -117,11 +118,18 @@ typedef struct swimsim_tuning {
                                  zero-initialised struct reads): every round hashes its dirty rows, as before ABI 11;
                                  2 = tests only: whenever a round follows in the call. Every read-back and every
                                  decision that needs a checksum still gets it; results are identical in every mode */
+    int32_t resp_echo;        /* echoed response records (ABI 14): may a ping or ping-req response leave out
+                                 a record that only repeats what the sender's message has just told the receiver (same
+                                 member, status and incarnation; never a tombstone record, never the sender's own
+                                 member)? Such a record cannot apply at the sender. -1 or 1 (default, also with a NULL
+                                 tuning block): yes; the entry is still counted, bumped and deleted as before, only its
+                                 record is not written. 0 (also what an older caller's zero-initialised struct reads):
+                                 every kept record is written, as before ABI 14. Results are identical either way */
 } swimsim_tuning;
 /* Environment, read at swimsim_create (A/B experiments; results are identical either way): SWIMSIM_SYNC_SPIN=0 waits for
  * the main stream's host round trips in the runtime's stream wait instead of polling an event; SWIMSIM_SIDE2=0 runs both
  * generations of side-stream checksum launches on one stream; SWIMSIM_CS_DEFER=0|1|2 overrides
- * swimsim_tuning.cs_defer; SWIMSIM_CS_DEFER_LOG=1 writes one stderr line per phase C that had a round to leave its rows
+ * swimsim_tuning.cs_defer; SWIMSIM_RESP_ECHO=0|1 overrides swimsim_tuning.resp_echo; SWIMSIM_CS_DEFER_LOG=1 writes one stderr line per phase C that had a round to leave its rows
  * to (round, dirty rows, rows written in the round, deferred decisions, carried or hashed). */
 
 /* Events applied in phase E of a round (docs/ROUND_SEMANTICS.md §4). */
@@ -458,7 +466,11 @@ int swimsim_kernel_times(swimsim_t *h, const char **names, double *avg_ms, uint6
 int swimsim_enable_timing(swimsim_t *h, int32_t enable);
 /* the unit counts behind those byte figures since swimsim_enable_timing (rows hashed by each checksum kernel,
  * changes processed / applied by each merge kernel, records issued, ...): names[i], values[i]; "hot_slots" is
- * the number of hot-column slots in use now (not a count since the reset). The last three (ABI 11, lazy phase C,
+ * the number of hot-column slots in use now (not a count since the reset). "resp_echoed" (ABI 14,
+ * swimsim_tuning.resp_echo): direct-ping response records that were kept ("recv_issued" counts them, as do the protocol
+ * counter msg_changes and the bump) but not written, being echoes; "resp_merged" no longer counts them, so that
+ * resp_merged with resp_echo 0 = resp_merged + resp_echoed with resp_echo 1, and the "alg bytes" of the recv_merge and
+ * resp_merge families count fewer processed records than before ABI 14. The last three (ABI 11, lazy phase C,
  * swimsim_tuning.cs_defer): "cs_skipped_rounds" = rounds whose phase C hashed nothing, "cs_carried_rows" = the dirty rows
  * they left, summed over those rounds, "cs_forced" = rounds that would have skipped but deferred too many full-sync
  * decisions and hashed */

@@ -54,7 +54,10 @@ enum Counter {
     // dense row copies k_issue made for dirty senders (none since the pending-live state), and the
     // issue-time rows rebuilt instead: by a receive wave before the content would be lost (late), and at resolution
     // time for a decision that needs the sender's checksum (mat)
-    C_X_ISSUE_SNAPS, C_X_LAZY_LATE, C_X_LAZY_MAT, C_NALL
+    C_X_ISSUE_SNAPS, C_X_LAZY_LATE, C_X_LAZY_MAT,
+    // direct-ping response records IssueAsReceiver kept (counted, bumped) but did not write: echoes of what the sender
+    // had just sent (phase D only, the responses C_X_MERGED_R counts on the other side)
+    C_X_ECHO, C_NALL
 };
 
 constexpr int CTR_SHARDS = 64, CTR_STRIDE = 64;   // d.ctr is [CTR_SHARDS][CTR_STRIDE] u64

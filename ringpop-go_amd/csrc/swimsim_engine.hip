@@ -445,6 +445,7 @@ struct swimsim {
     uint32_t rounds_left = 0;                     // rounds of the running step call after the current one
     uint32_t round_deferred = 0;                  // full-sync decisions the current round's phases D and Q2 deferred
     bool cs_carried = false;                      // some row is dirty because a phase C skipped it
+    int resp_echo = 1;                            // swimsim_tuning.resp_echo: echoed response records are left out (k_recv)
     bool cs_defer_log = false;                    // SWIMSIM_CS_DEFER_LOG=1: one stderr line per phase C that could skip
     uint64_t cs_skipped_rounds = 0, cs_carried_rows = 0, cs_forced = 0, cs_units_base[3] = {0, 0, 0};
     bool colx_stale = false;                     // raw row writes marked every column: rebuilt at the next step
@@ -1275,6 +1276,7 @@ int run_waves(swimsim *h, int phase, uint32_t maxpairs) {
     RecvArgs a{};
     a.counts = h->counts; a.offs = h->offs; a.ulist = h->ulist;
     a.phase = phase;
+    a.echo = h->resp_echo;
     a.sdesc = phase == 0 ? h->sdesc : h->sdesc2;
     a.sI = phase == 0 ? h->sI : h->sI2;
     a.sC = phase == 0 ? h->sC : h->sC2;
@@ -1878,6 +1880,12 @@ int swimsim_create(const swimsim_config *cfg, swimsim_t **out) {
     if (const char *v = getenv("SWIMSIM_CS_DEFER_LOG")) h->cs_defer_log = atoi(v) != 0;
     if (h->cs_defer < 0 || h->cs_defer > 2) {
         h->err = "swimsim_tuning.cs_defer is -1, 0, 1 or 2";
+        return bail(SWIMSIM_EINVAL);
+    }
+    if (tun && tun->resp_echo >= 0) h->resp_echo = tun->resp_echo;
+    if (const char *v = getenv("SWIMSIM_RESP_ECHO")) h->resp_echo = atoi(v);   // (experiment: 0 = every kept record is written)
+    if (h->resp_echo < 0 || h->resp_echo > 1) {
+        h->err = "swimsim_tuning.resp_echo is -1, 0 or 1";
         return bail(SWIMSIM_EINVAL);
     }
     if (h->fault_inject & 32) h->csr_ecap = 24;      // (tests: rows whose exception entries end within CSR_EREG of the cap)
@@ -3082,7 +3090,9 @@ int swimsim_kernel_times(swimsim_t *h, const char **names, double *avg_ms, uint6
     // row. IssueAsReceiver's bytes are beside them (swimsim_kernel_units has every count apart)
     const double merge_bytes = merged * 22.0 + applied * 23.0;
     const double resp_bytes = delta(C_X_MERGED_R) * 22.0 + delta(C_X_APPLIED_R) * 23.0 + delta(C_X_BUMPED) * 24.0;
-    const double recv_issue_bytes = delta(C_X_RISSUED) * 36.0 + delta(C_X_RCALLS) * 4.0 * h->d.NBIT;
+    // (an echoed record is kept and bumped but not written: 16 B less. Its read on the other side is not in
+    // C_X_MERGED_R at all, so resp_merge counts fewer processed records than before the echo rule)
+    const double recv_issue_bytes = delta(C_X_RISSUED) * 36.0 - delta(C_X_ECHO) * 16.0 + delta(C_X_RCALLS) * 4.0 * h->d.NBIT;
     for (int f = 0; f < F_NFAM && (size_t)f < cap; f++) {
         if (names) names[f] = kFamName[f];
         if (avg_ms) avg_ms[f] = h->fam_n[f] ? h->fam_ms[f] / (double)h->fam_n[f] : 0.0;
@@ -3116,13 +3126,13 @@ int swimsim_kernel_units(swimsim_t *h, const char **names, double *values, size_
                                "bitmap_words_per_row", "hot_slots", "dense_resp", "dense_jobs", "jobs_applied",
                                "dense_heal", "defer", "defer_eq", "defer_norow", "defer_rep", "defer_undo",
                                "defer_rep_diff", "defer_undo_diff", "defer_fs", "defer_undo_over", "defer_clean",
-                               "issue_snaps", "lazy_late", "lazy_mat",
+                               "issue_snaps", "lazy_late", "lazy_mat", "resp_echoed",
                                "cs_skipped_rounds", "cs_carried_rows", "cs_forced"};
     const int ki[] = {C_X_CS_ROWS, C_X_CS_ROWS_N, C_X_CS_DUP, C_X_MERGED, C_X_APPLIED, C_X_RISSUED, C_X_RCALLS,
                       C_X_MERGED_R, C_X_APPLIED_R, C_X_BUMPED, C_X_ISSUED, -1, -2, C_X_DENSE_RESP, C_X_DENSE_JOBS,
                       C_X_JOBS_APPLIED, C_X_DENSE_HEAL, C_X_DEFER, C_X_DEFER_EQ, C_X_DEFER_NOROW, C_X_DEFER_REP,
                       C_X_DEFER_UNDO, C_X_DEFER_REP_DIFF, C_X_DEFER_UNDO_DIFF, C_X_DEFER_FS, C_X_DEFER_UNDO_OVER,
-                      C_X_DEFER_CLEAN, C_X_ISSUE_SNAPS, C_X_LAZY_LATE, C_X_LAZY_MAT,
+                      C_X_DEFER_CLEAN, C_X_ISSUE_SNAPS, C_X_LAZY_LATE, C_X_LAZY_MAT, C_X_ECHO,
                       -3, -4, -5};                                 // (-3..-5: lazy phase C, host counts)
     const uint64_t lazy_c[3] = {h->cs_skipped_rounds - h->cs_units_base[0], h->cs_carried_rows - h->cs_units_base[1],
                                 h->cs_forced - h->cs_units_base[2]};

@@ -433,10 +433,15 @@ __device__ __forceinline__ void merge_first(const DS &d, const MsgDesc &md, uint
     }
 }
 // (dctr >= 0: the measurement counter a dense message adds one to; pre0: the first batch from merge_first, or null;
-// ulog: the receive phase's undo log position of this row (k_recv), or null; lz: the row as a sender of the phase, k_recv)
+// ulog: the receive phase's undo log position of this row (k_recv), or null; lz: the row as a sender of the phase, k_recv;
+// echo: the wave's bitmap over hot slots in LDS (k_recv), or null: the bit of a record's slot is set when the row's word
+// for the member equals the record's pair once the record is merged, the record is no tombstone and its member is not
+// echo_sender, the message's sender. The response to that sender need not carry such a member (echoes).
+// The caller has cleared the bitmap; dense messages mark nothing)
 __device__ __forceinline__ void wave_merge_body(const DS &d, uint32_t ol, uint32_t o, const MsgDesc &md, uint32_t now_e,
                                                 uint32_t sched_r, MAcc &acc, int dctr, const uint4 *pre0 = nullptr,
-                                                uint32_t *ulog = nullptr, LazyCtx *lz = nullptr) {
+                                                uint32_t *ulog = nullptr, LazyCtx *lz = nullptr, uint32_t *echo = nullptr,
+                                                uint32_t echo_sender = 0) {
     const uint32_t *rowp = d.mw + (size_t)ol * d.NP;
     const uint32_t *hrow = d.hmw + (size_t)ol * d.HP;
     if (md.kind == 0) {
@@ -458,10 +463,17 @@ __device__ __forceinline__ void wave_merge_body(const DS &d, uint32_t ol, uint32
                 cur[u] = rec[u].x == 0xFFFFFFFFu ? 0u : hk[u] != SRC_NONE ? hrow[hk[u]] : rowp[rec_m(rec[u])];
 #pragma unroll
             for (int u = 0; u < MB; u++) {
-                const int before = acc.napp;
+                const int before = acc.napp, refuted = acc.nref;
                 if (rec[u].x != 0xFFFFFFFFu)
                     merge_change_w(d, ol, o, rec_m(rec[u]), cur[u], rec_st(rec[u]), rec_e(rec[u]), rec[u].z, rec[u].w, now_e,
                                    sched_r, acc, hk[u]);
+                if (echo && hk[u] != SRC_NONE) {                   // (hk is SRC_NONE for the padding records too)
+                    // the row's word now: the record's pair if it applied and was no refute, else what it was
+                    const uint32_t recw = (rec_e(rec[u]) << 3) | rec_st(rec[u]);
+                    const bool same = acc.napp != before ? acc.nref == refuted : cur[u] == recw;
+                    if (same && rec_st(rec[u]) != ST_TOMB && rec_m(rec[u]) != echo_sender)
+                        atomicOr(echo + (hk[u] >> 5), 1u << (hk[u] & 31));
+                }
                 if (ulog) {                                        // the overwritten word, in apply order
                     const bool ap = acc.napp != before;
                     const unsigned long long b = __ballot(ap);
@@ -482,6 +494,8 @@ __device__ __forceinline__ void wave_merge_body(const DS &d, uint32_t ol, uint32
         if (dctr >= 0 && lane_id() == 0) ctr_add(d, dctr, 1ull);
         if (ulog) *ulog = d.ulog_cap + 1u;                          // (not logged: the row's issue-time words are lost)
     }
+    // (the bitmap's strip belongs to this wave alone: a wave-level fence orders its LDS writes before the walk's reads)
+    if (echo) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __threadfence_block();
 }
 // cset selects the measurement counters (0: k_recv's C_X_MERGED/C_X_APPLIED, 1: k_resp's pair, 2: none, 3: the reverse
@@ -497,10 +511,12 @@ __device__ void wave_merge_msg(const DS &d, uint32_t ol, uint32_t o, const MsgDe
 __device__ __forceinline__ void wave_merge_msg_pre(const DS &d, uint32_t ol, uint32_t o, const MsgDesc &md, uint32_t now_e,
                                                    uint32_t sched_r, int cset, RowPre &p, int dctr = -1,
                                                    const uint4 *pre0 = nullptr, bool logit = false,
-                                                   LazyCtx *lz = nullptr) {
+                                                   LazyCtx *lz = nullptr, uint32_t *echo = nullptr,
+                                                   uint32_t echo_sender = 0) {
     MAcc acc;
     acc.tag = p.useq;
-    wave_merge_body(d, ol, o, md, now_e, sched_r, acc, dctr, pre0, logit && d.ulog ? &p.ulog : nullptr, lz);
+    wave_merge_body(d, ol, o, md, now_e, sched_r, acc, dctr, pre0, logit && d.ulog ? &p.ulog : nullptr, lz, echo,
+                    echo_sender);
     wave_finalize_pre(d, ol, acc, cset, p);
 }
 
@@ -609,36 +625,47 @@ __device__ __forceinline__ uint32_t wscan_excl(uint32_t v, uint32_t &total) {
 // (disseminator.go:128-133,201-215). Records are in member order within a lane's range; the order of
 // a message does not matter (its changes are distinct members).
 // (the body: cnt entries, maxP, the walk, the slots in use and the pool offset of cnt records are the caller's;
-// returns the records written, and for RECV the deleted entries in del / delnh, wave sums)
+// returns the entries kept, and for RECV the deleted entries in del / delnh, wave sums. echo (RECV only, or null): the
+// receive wave's bitmap of hot slots whose kept entry is an echo (wave_merge_body): such an entry is counted as kept,
+// bumped and deleted like any other, but its record is not written and takes no position, so out.len, the records
+// written, may be below the entries kept)
 template <bool RECV>
 __device__ __forceinline__ uint32_t wave_issue_body(const DS &d, uint32_t ol, uint32_t sender, uint32_t sinc, MsgDesc &out,
                                                     uint32_t cnt, int maxp, bool hotwalk, uint32_t nslots,
-                                                    unsigned long long off, int &del_out, int &delnh_out) {
+                                                    unsigned long long off, int &del_out, int &delnh_out,
+                                                    const uint32_t *echo = nullptr) {
     const size_t rb = (size_t)ol * d.NP, hb = (size_t)ol * d.HP;
     uint32_t *bits = d.dbit + (size_t)ol * d.NBIT;
-    uint32_t pos = 0;
+    uint32_t pos = 0;                                              // records written
+    uint32_t kept = 0;                                             // entries kept, this lane's (RECV with echo)
     int del = 0, delnh = 0;
+    const bool skip = RECV && echo != nullptr;
+    // (the bitmap word of slot hk, read beside the slot's cell and word, not after them: bit hk & 31 is the slot's)
+    auto echo_word = [&](uint32_t hk) { return skip && hk != SRC_NONE ? echo[hk >> 5] : 0u; };
     if (hotwalk) {
         // every buffered member of this row has a hot slot: walk the row's slots in use (a few KB,
         // contiguous) instead of the presence bitmap (N/8 bytes) and the gathers it leads to. Records come out in
         // slot order; the order of a message does not matter (its changes are distinct members).
         for (uint32_t base = 0; base < nslots; base += 64 * MB) {
             uint2 ce[MB];
-            uint32_t wv[MB], m[MB];
+            uint32_t wv[MB], m[MB], ew[MB];
 #pragma unroll
             for (int u = 0; u < MB; u++) {
                 const uint32_t k = base + u * 64 + lane_id();
                 ce[u] = k < nslots ? d.hde[hb + k] : make_uint2(DE_NONE, 0);
                 wv[u] = k < nslots ? d.hmw[hb + k] : 0u;
                 m[u] = k < nslots ? d.hlist[k] : 0u;
+                ew[u] = echo_word(k < nslots ? k : SRC_NONE);
             }
-            bool keep[MB];
+            bool keep[MB], wr[MB];
             uint32_t nk = 0;
 #pragma unroll
             for (int u = 0; u < MB; u++) {
                 const uint32_t src = de_src(ce[u].x);
                 keep[u] = de_p(ce[u].x) != DP_NONE && !(RECV && src == sender && ce[u].y == sinc);   // filterChangesFromSender
-                nk += keep[u] ? 1u : 0u;
+                wr[u] = keep[u] && !((ew[u] >> (lane_id() & 31)) & 1u);     // (slot base + 64 u + lane)
+                kept += keep[u] ? 1u : 0u;
+                nk += wr[u] ? 1u : 0u;
             }
             uint32_t tot;
             uint32_t at = pos + wscan_excl(nk, tot);
@@ -646,8 +673,10 @@ __device__ __forceinline__ uint32_t wave_issue_body(const DS &d, uint32_t ol, ui
             for (int u = 0; u < MB; u++) {
                 if (!keep[u]) continue;
                 const uint32_t st = (wv[u] & 7u) == ST_UNKNOWN ? ST_TOMB : (wv[u] & 7u);   // evicted: (tombstone, inc)
-                if (at < cnt) d.pool[off + at] = rec_make(m[u], st, wv[u] >> 3, de_src(ce[u].x), ce[u].y, base + u * 64 + lane_id() + 1u);
-                at++;
+                if (wr[u]) {
+                    if (at < cnt) d.pool[off + at] = rec_make(m[u], st, wv[u] >> 3, de_src(ce[u].x), ce[u].y, base + u * 64 + lane_id() + 1u);
+                    at++;
+                }
                 if (RECV) {                                                   // bump
                     const uint32_t k = base + u * 64 + lane_id();
                     uint32_t nx;
@@ -672,7 +701,7 @@ __device__ __forceinline__ uint32_t wave_issue_body(const DS &d, uint32_t ol, ui
         const uint32_t *drow = d.mw + rb;
         for (uint32_t base = 0; base < d.NP; base += 64 * MB) {
             uint2 ce[MB];
-            uint32_t wv[MB], hk[MB];
+            uint32_t wv[MB], hk[MB], ew[MB];
 #pragma unroll
             for (int u = 0; u < MB; u++) {
                 const uint32_t m = base + u * 64 + lane_id();
@@ -682,18 +711,22 @@ __device__ __forceinline__ uint32_t wave_issue_body(const DS &d, uint32_t ol, ui
                 wv[u] = in ? drow[m] : 0u;
             }
 #pragma unroll
-            for (int u = 0; u < MB; u++)
+            for (int u = 0; u < MB; u++) {
+                ew[u] = echo_word(hk[u]);
                 if (hk[u] != SRC_NONE) {
                     ce[u] = d.hde[hb + hk[u]];
                     wv[u] = d.hmw[hb + hk[u]];
                 }
-            bool keep[MB];
+            }
+            bool keep[MB], wr[MB];
             uint32_t nk = 0;
 #pragma unroll
             for (int u = 0; u < MB; u++) {
                 keep[u] = de_p(ce[u].x) != DP_NONE &&
                           !(RECV && de_src(ce[u].x) == sender && ce[u].y == sinc);   // filterChangesFromSender
-                nk += keep[u] ? 1u : 0u;
+                wr[u] = keep[u] && !((ew[u] >> (hk[u] & 31)) & 1u);
+                kept += keep[u] ? 1u : 0u;
+                nk += wr[u] ? 1u : 0u;
             }
             uint32_t tot;
             uint32_t at = pos + wscan_excl(nk, tot);
@@ -703,8 +736,10 @@ __device__ __forceinline__ uint32_t wave_issue_body(const DS &d, uint32_t ol, ui
                 bool gone = false;
                 if (keep[u]) {
                     const uint32_t st = (wv[u] & 7u) == ST_UNKNOWN ? ST_TOMB : (wv[u] & 7u);   // evicted: (tombstone, inc)
-                    if (at < cnt) d.pool[off + at] = rec_make(m, st, wv[u] >> 3, de_src(ce[u].x), ce[u].y, tag_of_slot(hk[u]));
-                    at++;
+                    if (wr[u]) {
+                        if (at < cnt) d.pool[off + at] = rec_make(m, st, wv[u] >> 3, de_src(ce[u].x), ce[u].y, tag_of_slot(hk[u]));
+                        at++;
+                    }
                     if (RECV) {                                               // bump
                         uint32_t nx;
                         if ((int)(de_p(ce[u].x) + 1) >= maxp) {
@@ -754,11 +789,12 @@ __device__ __forceinline__ uint32_t wave_issue_body(const DS &d, uint32_t ol, ui
                 else m[k] = 0xFFFFFFFFu;
             }
             uint2 ce[MB];                                        // the 8-byte entry and the member word
-            uint32_t wv[MB], hk[MB];
+            uint32_t wv[MB], hk[MB], ew[MB];
 #pragma unroll
             for (int k = 0; k < MB; k++) hk[k] = m[k] != 0xFFFFFFFFu ? hot_slot(d, m[k]) : SRC_NONE;
 #pragma unroll
             for (int k = 0; k < MB; k++) {
+                ew[k] = echo_word(hk[k]);
                 if (m[k] == 0xFFFFFFFFu) {
                     ce[k] = make_uint2(DE_NONE, 0);
                     wv[k] = 0u;
@@ -777,12 +813,14 @@ __device__ __forceinline__ uint32_t wave_issue_body(const DS &d, uint32_t ol, ui
                 p[k] = de_p(ce[k].x);
                 sr[k] = make_uint2(de_src(ce[k].x), ce[k].y);
             }
-            bool keep[MB];
+            bool keep[MB], wr[MB];
             uint32_t nk = 0;
 #pragma unroll
             for (int k = 0; k < MB; k++) {
                 keep[k] = m[k] != 0xFFFFFFFFu && !(RECV && sr[k].x == sender && sr[k].y == sinc);   // filterChangesFromSender
-                nk += keep[k] ? 1u : 0u;
+                wr[k] = keep[k] && !((ew[k] >> (hk[k] & 31)) & 1u);
+                kept += keep[k] ? 1u : 0u;
+                nk += wr[k] ? 1u : 0u;
             }
             uint32_t tot;
             uint32_t at = pos + wscan_excl(nk, tot);
@@ -790,8 +828,10 @@ __device__ __forceinline__ uint32_t wave_issue_body(const DS &d, uint32_t ol, ui
             for (int k = 0; k < MB; k++) {
                 if (!keep[k]) continue;
                 const uint32_t st = (wv[k] & 7u) == ST_UNKNOWN ? ST_TOMB : (wv[k] & 7u);   // evicted: (tombstone, inc)
-                if (at < cnt) d.pool[off + at] = rec_make(m[k], st, wv[k] >> 3, sr[k].x, sr[k].y, tag_of_slot(hk[k]));
-                at++;
+                if (wr[k]) {
+                    if (at < cnt) d.pool[off + at] = rec_make(m[k], st, wv[k] >> 3, sr[k].x, sr[k].y, tag_of_slot(hk[k]));
+                    at++;
+                }
                 if (RECV) {                                                   // bump
                     uint32_t nx;
                     if ((int)(p[k] + 1) >= maxp) {
@@ -825,7 +865,7 @@ __device__ __forceinline__ uint32_t wave_issue_body(const DS &d, uint32_t ol, ui
     out.off_lo = (uint32_t)off;
     out.off_hi = (uint32_t)(off >> 32);
     out.len = min(pos, cnt);
-    return out.len;
+    return skip ? min((uint32_t)wsum((int)kept), cnt) : out.len;
 }
 
 template <bool RECV>
@@ -1556,6 +1596,7 @@ struct RecvArgs {
     int phase;                                      // 0: direct ping (phase D), 1: ping-req (Q2)
     const MsgDesc *sdesc;                           // sender snapshots (by global sender id)
     const uint32_t *sI, *sC;
+    int echo;                                       // swimsim_tuning.resp_echo: echoed records are left out of responses
     uint32_t *sS;                                   // lazy sender checksum: dense slot of the sender's row, SRC_PEND
                                                     // (pending, live: published here if a receive wave rebuilds it), or none
     MsgDesc *rdesc;                                 // responses (by sender id / sender id * K + slot)
@@ -1625,16 +1666,20 @@ __global__ void k_pair_info(const DS d, const uint32_t *vals_in, const uint32_t 
 // heal rounds did, sharded): a dense message, or a bound above 4,096 records or a sixteenth of a sub-pool, allocates
 // the exact count after the merge (at most 4,096 spare records per receiver).
 __device__ __forceinline__ void recv_one_pre(const DS &d, const RecvArgs &a, uint32_t j, const uint4 pi0, const uint4 pi1,
-                                             uint32_t pair, uint32_t nslots, uint32_t now, RowPre &p, LazyCtx &lz) {
+                                             uint32_t pair, uint32_t nslots, uint32_t now, RowPre &p, LazyCtx &lz,
+                                             uint32_t *echo) {
     const uint32_t ol = j - d.lo;
     const uint32_t v = pi1.w, sender = a.phase == 0 ? v : v / d.K, resp_idx = v;
     MsgDesc md;
     md.off_lo = pi0.x; md.off_hi = pi0.y; md.len = pi0.z; md.kind = pi0.w;
+    if (md.kind != 0) echo = nullptr;                              // (a dense message marks nothing)
+    if (echo)                                                      // (the words covering the slots in use)
+        for (uint32_t i = lane_id(); i < (nslots + 31u) / 32u; i += 64) echo[i] = 0u;
     const uint64_t bound = (uint64_t)(uint32_t)p.dcnt + md.len;
     const bool early = md.kind == 0 && bound > 0 && bound <= min(4096ull, d.pool_cap / POOL_SHARDS / 16);
     unsigned long long roff = 0;
     if (early && lane_id() == 0) roff = pool_alloc_lane0(d, (uint32_t)bound);   // (read after the merge)
-    wave_merge_msg_pre(d, ol, j, md, now, now, 0, p, -1, nullptr, true, &lz);
+    wave_merge_msg_pre(d, ol, j, md, now, now, 0, p, -1, nullptr, true, &lz, echo, sender);
     MsgDesc resp;
     resp.kind = 0; resp.len = 0; resp.off_lo = resp.off_hi = 0;
     uint32_t kept = 0;
@@ -1644,7 +1689,7 @@ __device__ __forceinline__ void recv_one_pre(const DS &d, const RecvArgs &a, uin
         if (off != ~0ull) {
             int del = 0, delnh = 0;
             kept = wave_issue_body<true>(d, ol, sender, pi1.x, resp, cnt, p.maxp, d.hidx && p.nhe == 0, nslots, off, del,
-                                         delnh);
+                                         delnh, echo);
             if (del) { p.dcnt -= del; if (lane_id() == 0) d.dcnt[ol] = p.dcnt; }
             if (delnh) { p.nhe -= delnh; if (lane_id() == 0) d.nhe[ol] = p.nhe; }
             __threadfence_block();
@@ -1653,6 +1698,7 @@ __device__ __forceinline__ void recv_one_pre(const DS &d, const RecvArgs &a, uin
     if (lane_id() == 0) {
         ctr_add(d, C_X_RISSUED, (unsigned long long)kept);
         ctr_add(d, C_X_RCALLS, 1ull);
+        if (a.phase == 0 && kept != resp.len) ctr_add(d, C_X_ECHO, (unsigned long long)(kept - resp.len));
     }
     if (kept == 0) {
         const uint32_t scs = pi1.y;
@@ -1680,7 +1726,8 @@ __device__ __forceinline__ void recv_one_pre(const DS &d, const RecvArgs &a, uin
     }
     if (lane_id() == 0) {
         a.rdesc[resp_idx] = resp;
-        if (resp.kind != 2) ctr_add(d, C_MSG_CHANGES, (unsigned long long)resp.len);
+        // (msg_changes counts the filtered list, echoes included: kept; a full sync's dense list: its known members)
+        if (resp.kind != 2) ctr_add(d, C_MSG_CHANGES, (unsigned long long)(resp.kind == 0 ? kept : resp.len));
         if (a.phase == 1) {
             ctr_add(d, C_HELPER_CALLS, 1ull);
             ctr_add(d, C_MSG_CHANGES, (unsigned long long)md.len);
@@ -1697,7 +1744,11 @@ __device__ __forceinline__ void recv_one_pre(const DS &d, const RecvArgs &a, uin
 // gather-latency bound (each message is a chain of dependent loads: pair snapshot, record, row word, then the stores),
 // so resident waves, not registers, set the pace
 constexpr int RECV_MIN_WAVES = 4;
+// (echo_bits: one strip per wave of a bit per hot slot, 4 KB per workgroup: no occupancy lost at 4 waves per SIMD)
+constexpr uint32_t ECHO_WORDS = (RT_MAXSLOTS + 31u) / 32u + 2u;    // (every tag value below RT_COLD lands inside: 8,192 bits)
+static_assert(ECHO_WORDS * 32u >= RT_COLD, "a record's slot tag indexes the echo bitmap");
 __global__ void __launch_bounds__(256, RECV_MIN_WAVES) k_recv(DS d, RecvArgs a) {
+    __shared__ uint32_t echo_bits[4][ECHO_WORDS];                  // (the launch bound's 256 threads: 4 waves)
     const uint32_t w = wave_gid();
     if (w >= d.NL) return;
     const uint32_t u = a.ulist[w];                                  // (read beside the count; stale past it, never used)
@@ -1709,9 +1760,10 @@ __global__ void __launch_bounds__(256, RECV_MIN_WAVES) k_recv(DS d, RecvArgs a) 
     LazyCtx lz;
     lz.sS = a.sS; lz.sI = a.sI;
     lz.pend = a.sS && d.ulog && uni(a.sS[key]) == SRC_PEND;        // this row is a pending-live sender of the phase
+    uint32_t *echo = a.echo && d.hidx ? echo_bits[(threadIdx.x >> 6) & 3u] : nullptr;
     for (uint32_t w = 0; w < n; w++) {
         const uint32_t pair = off + w;
-        recv_one_pre(d, a, key, a.pinfo[2 * (size_t)pair], a.pinfo[2 * (size_t)pair + 1], pair, nslots, now, p, lz);
+        recv_one_pre(d, a, key, a.pinfo[2 * (size_t)pair], a.pinfo[2 * (size_t)pair + 1], pair, nslots, now, p, lz, echo);
     }
     if (d.ulog_cnt && lane_id() == 0) d.ulog_cnt[key - d.lo] = min(p.ulog, d.ulog_cap + 1u);
 }
@@ -2090,7 +2142,8 @@ __global__ void k_resp(DS d, const int32_t *tgt, const uint8_t *failed, const Ms
     uint4 rec0[MB];                                                 // (the response's first records ride with the bump's
     merge_first(d, rd, rec0);                                       // loads: the pool is read-only here)
     wave_bump_pre(d, ol, sd, p);
-    wave_merge_msg_pre(d, ol, o, rd, now, now, 1, p, C_X_DENSE_RESP, rec0);
+    if (rd.kind != 0 || rd.len)                                    // (an empty response: no merge, no reductions)
+        wave_merge_msg_pre(d, ol, o, rd, now, now, 1, p, C_X_DENSE_RESP, rec0);
     if (lane_id() == 0) {
         ctr_add(d, C_PINGS_OK, 1ull);
         if (sd.kind == 0) ctr_add(d, C_X_BUMPED, (unsigned long long)sd.len);
@@ -2111,7 +2164,8 @@ __global__ void k_resolve(DS d, const int32_t *tgt, const uint8_t *failed, const
             errs++;
             wave_bump(d, ol, sdesc2[o]);                            // bump only on error (105-106)
         } else {
-            wave_merge_msg(d, ol, o, rdesc2[(size_t)o * K + q], now, now, 2, C_X_DENSE_RESP);
+            const MsgDesc rd = rdesc2[(size_t)o * K + q];
+            if (rd.kind != 0 || rd.len) wave_merge_msg(d, ol, o, rd, now, now, 2, C_X_DENSE_RESP);
         }
     }
     if (lane_id() == 0) {

@@ -61,7 +61,8 @@ class Tuning(C.Structure):
     """swimsim_tuning (include/swimsim.h): engine variants for tests and diagnostics, -1 = the production default."""
     _fields_ = [("hot_slots", C.c_int32), ("dense_slots", C.c_int32), ("cs_async", C.c_int32),
                 ("cs_async_rows", C.c_int32), ("cs_narrow_rows", C.c_int32), ("cs_ref", C.c_int32),
-                ("fault_inject", C.c_int32), ("defer_test", C.c_int32), ("cs_defer", C.c_int32)]
+                ("fault_inject", C.c_int32), ("defer_test", C.c_int32), ("cs_defer", C.c_int32),
+                ("resp_echo", C.c_int32)]
 
 
 def make_tuning(tuning):
