@@ -28,7 +28,9 @@
 extern "C" {
 #endif
 
-#define SWIMSIM_ABI_VERSION 14   /* 14: swimsim_tuning.resp_echo and the unit "resp_echoed" (results unchanged).
+#define SWIMSIM_ABI_VERSION 15   /* 15: swimsim_ring_checksums, swimsim_ring_census and swimsim_ring_times (read-only; the
+                                    results of every earlier call unchanged).
+                                    14: swimsim_tuning.resp_echo and the unit "resp_echoed" (results unchanged).
                                     13: swimsim_pool_usage (a read-back; nothing else changed since 12). 12: the
                                     checksum block-stream dump call is gone (only a diagnostics build ever
                                     implemented it, and that build is gone); nothing else changed since 11 */
@@ -456,6 +458,65 @@ int swimsim_route_n(swimsim_t *h, const uint8_t *keys, const uint64_t *off, size
 int swimsim_replica_census(swimsim_t *h, const uint8_t *keys, const uint64_t *off, size_t nkeys, uint32_t replica_points,
                            uint32_t n, int32_t who, int32_t mode, uint32_t *counted, uint64_t *hist_off,
                            int32_t *hist_member, uint32_t *hist_count, size_t cap, size_t *nhist, double *ms);
+
+/* ---- ring checksums through every node's own ring view (ABI 15) ----
+ * Ringpop.Checksum (ringpop.go:571-577) returns hashring.Checksum: Fingerprint32 of the ring's servers, sorted and
+ * joined by ";" (hashring.go:100-107). A node publishes it as the ring.checksum gauge and the ring.checksum-periodic
+ * stat (ringpop.go:209-217, 502-504) and in /admin/stats (stats_handler.go:56); two nodes with different ring checksums
+ * route some keys differently. These calls answer it, on the device, for every observer row of the handle. They are
+ * read-only as the ABI 8-10 calls are: no state and no result of a round changes.
+ *
+ * The servers of view o are the members whose cell in row o is alive or suspect: the set of ABI 9 and 10.
+ * ringcs(o) = Fingerprint32(S), S = the servers' addresses in ascending member index joined by ";" with no trailing
+ * separator. The addresses of a handle are fixed-width (W = 13..20 bytes) and strictly ascending, so sort.Strings order
+ * is index order, and S has cnt * (W + 1) - 1 bytes for cnt servers: the empty string for an empty view (3696677242),
+ * one address (13..20 bytes) for cnt = 1, at least 27 bytes otherwise. The synthetic addresses of members 0..4 give
+ * 2141723838. This is not the membership checksum of swimsim_checksums: incarnations and the alive / suspect
+ * distinction do not enter it.
+ *
+ * No deviation: Ringpop.handleChanges adds a server on alive and suspect and removes it on every other status
+ * (ringpop.go:550-563), and the checksum is a function of the server SET alone, so a real node's value is exactly this
+ * one whatever its history. The shared-hash history deviation of ABI 9 and 10 concerns replica points, which the
+ * checksum does not read.
+ *
+ * swimsim_ring_checksums: checksums[j] = ringcs(observers[j]); servers[j] (may be NULL) = that view's server count.
+ * observers must be rows of this handle; duplicates are allowed; observers = NULL means every owned row in order, and
+ * nobs must then be the number of owned rows. The read-back is proportional to nobs.
+ *
+ * swimsim_ring_census: who = SWIMSIM_CENSUS_LIVE or SWIMSIM_CENSUS_ALL selects the counted rows as for swimsim_census;
+ * *counted = their number. One entry per distinct checksum value over the counted rows, ascending by checksum:
+ * hist_count = the counted rows that answer it, hist_first = the lowest global observer index among them, hist_servers
+ * = that row's server count. Two different views with equal checksums form one entry, as the gauge would show. The
+ * counts sum to *counted. *nhist = the number of entries; at most cap are written and the caller retries with larger
+ * buffers (no error, as swimsim_route_census). No counted rows: *counted = 0 and *nhist = 0.
+ *
+ * mode: results are identical in every mode. 0 = production: rows whose views are equal share one FarmHash chain. Rows
+ * are grouped by a 64-bit order-free key of the server set and the server count, every grouped row is then compared
+ * with its group's lowest row member by member on the device, and a row that differs runs its own chain: a key
+ * collision never gives a wrong checksum. 1 = every row runs its own chain. 2 = tests only: the grouping key is
+ * narrowed to 3 bits, so that unequal views share a key and only the exact comparison parts them (the precedent is
+ * fault_inject 8 on the membership path). *hashed (may be NULL) = the chains the call ran: the rows in mode 1; in mode
+ * 0 the distinct views among the rows unless two views share the key, then more, never fewer. ms (may be NULL) = the
+ * HIP-event time of the device work; swimsim_ring_times gives the last call's split over the scan, the exact
+ * comparison and the chains with their scatter.
+ *
+ * At most three host synchronisations per call: the keys (12 bytes per row), the comparison's flags (4 bytes per row;
+ * only when some group has more than one row) and the checksums. Memory: 36 bytes per requested row, allocated on
+ * first use and freed at destroy: a handle that never calls these launches what it launched and keeps the
+ * swimsim_memory figures it had.
+ *
+ * SWIMSIM_EINVAL, before any device work and with nothing written: NULL handle (-1) or NULL required output; nobs = 0;
+ * NULL observers with nobs not the number of owned rows; an observer out of range or not owned; an unknown who or mode;
+ * N above 524,288 (the bound of the route calls' LDS bitmap). SWIMSIM_ENOMEM leaves the handle usable.
+ *
+ * Shards: a handle answers for its own rows; histograms add per checksum across shards, hist_first is the minimum and
+ * hist_servers follows it. */
+int swimsim_ring_checksums(swimsim_t *h, const uint32_t *observers, size_t nobs, int32_t mode, uint32_t *checksums,
+                           uint32_t *servers, uint32_t *hashed, double *ms);
+int swimsim_ring_census(swimsim_t *h, int32_t who, int32_t mode, uint32_t *counted, uint32_t *hist_checksum,
+                        uint32_t *hist_count, uint32_t *hist_servers, uint32_t *hist_first, size_t cap, size_t *nhist,
+                        uint32_t *hashed, double *ms);
+int swimsim_ring_times(swimsim_t *h, double *scan_ms, double *group_ms, double *hash_ms);
 
 /* ---- measurement ---- */
 /* average device time (ms) of each kernel family since the last reset, for roofline reporting */

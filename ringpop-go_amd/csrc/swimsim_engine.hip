@@ -8,6 +8,7 @@
 #include "swimsim_xchg.hip"
 #include "swimsim_census.hip"
 #include "swimsim_route.hip"
+#include "swimsim_ringcs.hip"
 
 #include <hipcub/hipcub.hpp>
 #include <rccl/rccl.h>
@@ -427,6 +428,15 @@ struct swimsim {
     size_t rt_bytes_cap = 0, rt_keys_cap = 0, rt_rows_cap = 0, rt_own_cap = 0, rt_exc_cap = 0, rt_cub_bytes = 0;
     std::vector<uint64_t> rt_rel;                 // the key offsets as uploaded (relative to the first key's byte)
     hipEvent_t rt_ev[2] = {nullptr, nullptr};
+    // ring checksums (swimsim_ring_checksums / swimsim_ring_census, swimsim_ringcs.hip), allocated at the first call and
+    // kept until destroy, rc_cap entries each: the rows' grouping keys and server counts, their representatives, the
+    // verify flags, the positions to hash, the representatives' checksums and every row's checksum. The rows
+    // themselves go through rt_rows; rc_split = the scan / group / hash device times of the last call
+    unsigned long long *rc_key = nullptr;
+    uint32_t *rc_cnt = nullptr, *rc_rep = nullptr, *rc_dif = nullptr, *rc_hl = nullptr, *rc_csr = nullptr, *rc_out = nullptr;
+    size_t rc_cap = 0;
+    bool rc_lds = false;
+    double rc_split[3] = {0, 0, 0};
     // reference-row checksum path (swimsim_checksum_ref.hip + swimsim_checksum_csr.hip), allocated at its first launch
     // (on for wide launches by default: the bench window runs 9.51 against 10.48 ms per round)
     int csr_mode = 1;                             // swimsim_tuning.cs_ref: 0 off, 1 wide launches, 2 every launch of
@@ -3044,7 +3054,7 @@ int swimsim_trace_read(swimsim_t *h, uint32_t *rounds, uint32_t *nlive, uint32_t
     return SWIMSIM_OK;
 }
 
-// key routing and replica sets through the observers' ring views
+// key routing, replica sets and ring checksums through the observers' ring views
 #include "swimsim_route_host.hip"
 
 int swimsim_enable_timing(swimsim_t *h, int32_t enable) {

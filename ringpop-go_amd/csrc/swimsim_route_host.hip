@@ -1,5 +1,6 @@
 // swimsim_route_host.hip — the host side of key routing and replica sets: swimsim_route, swimsim_route_census,
-// swimsim_route_n and swimsim_replica_census (kernels: swimsim_route.hip). Part of
+// swimsim_route_n and swimsim_replica_census (kernels: swimsim_route.hip), and of the ring
+// checksums: swimsim_ring_checksums and swimsim_ring_census (kernels: swimsim_ringcs.hip). Part of
 // swimsim_engine.hip, which includes it after struct swimsim and the helpers it uses (dalloc, stream_sync, DeviceScope).
 
 // ---- key routing through the observers' ring views (swimsim_route.hip) ----
@@ -539,4 +540,214 @@ int swimsim_replica_census(swimsim_t *h, const uint8_t *keys, const uint64_t *of
         return h->fail(SWIMSIM_EHIP, "replica census: %llu exceptions of one key over %u rows, n = %u", cur, h->NL, n);
     };
     return route_census_passes(h, nkeys, launch, emit, one_key_error, hist_off, hist_member, hist_count, cap, nhist, ms);
+}
+
+// ---- ring checksums through the observers' ring views (swimsim_ringcs.hip) ----
+namespace {
+
+int ringcs_check(swimsim *h, int32_t mode, const char *what) {
+    if (mode < 0 || mode > 2) return h->fail(SWIMSIM_EINVAL, "%s: unknown mode %d", what, mode);
+    if (h->N > ROUTE_N_MAX) return h->fail(SWIMSIM_EINVAL, "%s: %u members are more than %u", what, h->N, ROUTE_N_MAX);
+    return 0;
+}
+
+// the scratch of n requested rows, on first use
+int ringcs_scratch(swimsim *h, size_t n) {
+    if (n > h->rc_cap) {
+        if (h->rc_key) HIPCHK(h, stream_sync(h));
+        const size_t o = h->rc_cap;
+        auto drop = [&](size_t c) {
+            dfree(h, &h->rc_key, dalloc_bytes(c, 8));
+            dfree(h, &h->rc_cnt, dalloc_bytes(c, 4));
+            dfree(h, &h->rc_rep, dalloc_bytes(c, 4));
+            dfree(h, &h->rc_dif, dalloc_bytes(c, 4));
+            dfree(h, &h->rc_hl, dalloc_bytes(c, 4));
+            dfree(h, &h->rc_csr, dalloc_bytes(c, 4));
+            dfree(h, &h->rc_out, dalloc_bytes(c, 4));
+        };
+        drop(o);
+        h->rc_cap = 0;
+        const size_t c = n + n / 2;
+        int rc = 0;
+        if ((rc = dalloc(h, &h->rc_key, c, "ring checksum keys")) || (rc = dalloc(h, &h->rc_cnt, c, "ring checksum server counts")) ||
+            (rc = dalloc(h, &h->rc_rep, c, "ring checksum representatives")) || (rc = dalloc(h, &h->rc_dif, c, "ring checksum verify flags")) ||
+            (rc = dalloc(h, &h->rc_hl, c, "ring checksum hash list")) || (rc = dalloc(h, &h->rc_csr, c, "ring checksum chains")) ||
+            (rc = dalloc(h, &h->rc_out, c, "ring checksums"))) {
+            drop(c);                                                 // (a buffer that was not allocated is skipped)
+            (void)hipGetLastError();
+            return rc;
+        }
+        h->rc_cap = c;
+    }
+    if (int rc = route_grow(h, &h->rt_rows, &h->rt_rows_cap, n, "route rows")) return rc;
+    for (hipEvent_t &e : h->rt_ev)
+        if (!e) HIPCHK(h, hipEventCreate(&e));
+    if (!h->rc_lds) {                                                // (N above ~262,000: bitmap and static LDS pass 64 KB)
+        if ((size_t)route_bitmap_bytes(h->NP) + RINGCS_STATIC_LDS > 65536) {
+            HIPCHK(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_ringcs_hash), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                          (int)route_bitmap_bytes(h->NP)));
+            HIPCHK(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_ringcs_scan), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                          (int)route_bitmap_bytes(h->NP)));
+        }
+        h->rc_lds = true;
+    }
+    return 0;
+}
+
+// The checksums and server counts of the listed local rows (duplicates allowed), in list order. Three host
+// synchronisations at most: the keys, the verify flags (only when some row has a representative other than itself),
+// the checksums. *hashed = the chains run.
+int ringcs_run(swimsim *h, const std::vector<uint32_t> &rows, int32_t mode, uint32_t *cs, uint32_t *srv, uint32_t *hashed,
+               double *ms) {
+    const size_t n = rows.size();
+    if (int rc = ringcs_scratch(h, n)) return rc;
+    const uint32_t nn = (uint32_t)n, lds = route_bitmap_bytes(h->NP);
+    float t = 0;
+    // 1. scan
+    HIPCHK(h, hipMemcpyAsync(h->rt_rows, rows.data(), n * 4, hipMemcpyHostToDevice, h->s));
+    HIPCHK(h, hipEventRecord(h->rt_ev[0], h->s));
+    hipLaunchKernelGGL(k_ringcs_scan, dim3(nn), dim3(RINGCS_THREADS), lds, h->s, h->d, h->rt_rows, h->rc_key, h->rc_cnt);
+    HIPCHK(h, hipEventRecord(h->rt_ev[1], h->s));
+    std::vector<unsigned long long> key(n);
+    std::vector<uint32_t> cnt(n), rep(n), dif;
+    HIPCHK(h, hipMemcpyAsync(key.data(), h->rc_key, n * 8, hipMemcpyDeviceToHost, h->s));
+    HIPCHK(h, hipMemcpyAsync(cnt.data(), h->rc_cnt, n * 4, hipMemcpyDeviceToHost, h->s));
+    HIPCHK(h, stream_sync(h));                                       // synchronisation 1: 12 bytes per row
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipEventElapsedTime(&t, h->rt_ev[0], h->rt_ev[1]));
+    h->rc_split[0] = t;
+    h->rc_split[1] = h->rc_split[2] = 0;
+    // 2. group: rows of equal (key, cnt) under their lowest row (mode 2: 3 bits of the key alone; mode 1: no groups)
+    bool grouped = false;
+    for (uint32_t j = 0; j < nn; j++) rep[j] = j;
+    if (mode != 1) {
+        std::vector<uint32_t> order(n);
+        for (uint32_t j = 0; j < nn; j++) order[j] = j;
+        auto gk = [&](uint32_t j) { return mode == 2 ? std::make_pair(key[j] & 7ull, 0u) : std::make_pair(key[j], cnt[j]); };
+        std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) {
+            const auto ka = gk(a), kb = gk(b);
+            if (ka != kb) return ka < kb;
+            return rows[a] != rows[b] ? rows[a] < rows[b] : a < b;
+        });
+        for (size_t i = 0; i < n;) {
+            size_t e = i + 1;
+            while (e < n && gk(order[e]) == gk(order[i])) e++;
+            for (size_t q = i; q < e; q++) rep[order[q]] = order[i];
+            grouped |= e - i > 1;
+            i = e;
+        }
+    }
+    if (grouped) {                                                   // the exact comparison with the representative
+        dif.resize(n);
+        HIPCHK(h, hipMemcpyAsync(h->rc_rep, rep.data(), n * 4, hipMemcpyHostToDevice, h->s));
+        HIPCHK(h, hipMemsetAsync(h->rc_dif, 0, n * 4, h->s));
+        HIPCHK(h, hipEventRecord(h->rt_ev[0], h->s));
+        hipLaunchKernelGGL(k_ringcs_verify, dim3(nn), dim3(RINGCS_THREADS), 0, h->s, h->d, h->rt_rows, h->rc_rep, nn, h->rc_dif);
+        HIPCHK(h, hipEventRecord(h->rt_ev[1], h->s));
+        HIPCHK(h, hipMemcpyAsync(dif.data(), h->rc_dif, n * 4, hipMemcpyDeviceToHost, h->s));
+        HIPCHK(h, stream_sync(h));                                   // synchronisation 2: 4 bytes per row
+        HIPCHK(h, hipGetLastError());
+        HIPCHK(h, hipEventElapsedTime(&t, h->rt_ev[0], h->rt_ev[1]));
+        h->rc_split[1] = t;
+        for (uint32_t j = 0; j < nn; j++)
+            if (dif[j]) rep[j] = j;                                  // a key collision: the row runs its own chain
+    }
+    // 3. hash the representatives, 4. scatter
+    std::vector<uint32_t> hl;
+    for (uint32_t j = 0; j < nn; j++)
+        if (rep[j] == j) hl.push_back(j);
+    HIPCHK(h, hipMemcpyAsync(h->rc_rep, rep.data(), n * 4, hipMemcpyHostToDevice, h->s));
+    HIPCHK(h, hipMemcpyAsync(h->rc_hl, hl.data(), hl.size() * 4, hipMemcpyHostToDevice, h->s));
+    HIPCHK(h, hipEventRecord(h->rt_ev[0], h->s));
+    hipLaunchKernelGGL(k_ringcs_hash, dim3((uint32_t)hl.size()), dim3(RINGCS_THREADS), lds, h->s, h->d, h->rt_rows, h->rc_hl, h->rc_csr);
+    hipLaunchKernelGGL(k_ringcs_scatter, dim3(blocks_for_threads(nn)), dim3(256), 0, h->s, h->rc_rep, h->rc_csr, nn, h->rc_out);
+    HIPCHK(h, hipEventRecord(h->rt_ev[1], h->s));
+    HIPCHK(h, hipMemcpyAsync(cs, h->rc_out, n * 4, hipMemcpyDeviceToHost, h->s));
+    HIPCHK(h, stream_sync(h));                                       // synchronisation 3: 4 bytes per row
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipEventElapsedTime(&t, h->rt_ev[0], h->rt_ev[1]));
+    h->rc_split[2] = t;
+    if (srv) memcpy(srv, cnt.data(), n * 4);
+    if (hashed) *hashed = (uint32_t)hl.size();
+    if (ms) *ms = h->rc_split[0] + h->rc_split[1] + h->rc_split[2];
+    return SWIMSIM_OK;
+}
+
+}  // namespace
+
+int swimsim_ring_checksums(swimsim_t *h, const uint32_t *observers, size_t nobs, int32_t mode, uint32_t *checksums,
+                           uint32_t *servers, uint32_t *hashed, double *ms) {
+    if (!h) return SWIMSIM_EINVAL;
+    if (!checksums) return h->fail(SWIMSIM_EINVAL, "ring checksums: no output buffer");
+    if (nobs == 0) return h->fail(SWIMSIM_EINVAL, "ring checksums: no observers");
+    if (int rc = ringcs_check(h, mode, "ring checksums")) return rc;
+    if (!observers && nobs != h->NL)
+        return h->fail(SWIMSIM_EINVAL, "ring checksums: every owned row means nobs = %u, not %zu", h->NL, nobs);
+    if (nobs > 0xFFFFFFFFull) return h->fail(SWIMSIM_EINVAL, "ring checksums: list of %zu observers too long", nobs);
+    std::vector<uint32_t> rows(nobs);
+    for (size_t j = 0; j < nobs; j++) {
+        if (observers && (observers[j] < h->lo || observers[j] >= h->lo + h->NL))
+            return h->fail(SWIMSIM_EINVAL, "ring checksums: observer %u is not a row of this handle", observers[j]);
+        rows[j] = observers ? observers[j] - h->lo : (uint32_t)j;
+    }
+    DeviceScope ds(h->device);
+    std::vector<uint32_t> cs(nobs), srv(nobs);                       // (the outputs are written only by a call that succeeds)
+    uint32_t nh = 0;
+    double t = 0;
+    if (int rc = ringcs_run(h, rows, mode, cs.data(), srv.data(), &nh, &t)) return rc;
+    memcpy(checksums, cs.data(), nobs * 4);
+    if (servers) memcpy(servers, srv.data(), nobs * 4);
+    if (hashed) *hashed = nh;
+    if (ms) *ms = t;
+    return SWIMSIM_OK;
+}
+
+int swimsim_ring_census(swimsim_t *h, int32_t who, int32_t mode, uint32_t *counted, uint32_t *hist_checksum, uint32_t *hist_count,
+                        uint32_t *hist_servers, uint32_t *hist_first, size_t cap, size_t *nhist, uint32_t *hashed, double *ms) {
+    if (!h) return SWIMSIM_EINVAL;
+    if (!counted || !nhist || (cap && (!hist_checksum || !hist_count || !hist_servers || !hist_first)))
+        return h->fail(SWIMSIM_EINVAL, "ring census: no output buffer");
+    if (who != SWIMSIM_CENSUS_LIVE && who != SWIMSIM_CENSUS_ALL) return h->fail(SWIMSIM_EINVAL, "ring census: unknown who %d", who);
+    if (int rc = ringcs_check(h, mode, "ring census")) return rc;
+    std::vector<uint32_t> rows;
+    for (uint32_t r = 0; r < h->NL; r++)
+        if (who == SWIMSIM_CENSUS_ALL || h->live[h->lo + r]) rows.push_back(r);
+    const size_t n = rows.size();
+    uint32_t nh = 0;
+    double t = 0;
+    std::vector<uint32_t> cs(n), srv(n);
+    if (n) {
+        DeviceScope ds(h->device);
+        if (int rc = ringcs_run(h, rows, mode, cs.data(), srv.data(), &nh, &t)) return rc;
+    }
+    // one entry per distinct checksum, ascending; the rows ascend, so the first row of a run is its lowest observer
+    std::vector<uint32_t> order(n);
+    for (uint32_t j = 0; j < n; j++) order[j] = j;
+    std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return cs[a] < cs[b]; });
+    size_t total = 0;
+    for (size_t i = 0; i < n;) {
+        size_t e = i + 1;
+        while (e < n && cs[order[e]] == cs[order[i]]) e++;
+        if (total < cap) {
+            hist_checksum[total] = cs[order[i]];
+            hist_count[total] = (uint32_t)(e - i);
+            hist_servers[total] = srv[order[i]];
+            hist_first[total] = h->lo + rows[order[i]];
+        }
+        total++;
+        i = e;
+    }
+    *counted = (uint32_t)n;
+    *nhist = total;
+    if (hashed) *hashed = nh;
+    if (ms) *ms = t;
+    return SWIMSIM_OK;
+}
+
+int swimsim_ring_times(swimsim_t *h, double *scan_ms, double *group_ms, double *hash_ms) {
+    if (!h || !scan_ms || !group_ms || !hash_ms) return SWIMSIM_EINVAL;
+    *scan_ms = h->rc_split[0];
+    *group_ms = h->rc_split[1];
+    *hash_ms = h->rc_split[2];
+    return SWIMSIM_OK;
 }

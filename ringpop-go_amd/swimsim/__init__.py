@@ -37,6 +37,8 @@ T0_MS = 1_500_000_000_000
 CENSUS_LIVE, CENSUS_ALL = 0, 1                   # swimsim_census `who`
 CENSUS_WHO = {"live": CENSUS_LIVE, "all": CENSUS_ALL}
 ROUTE_N_REPLICAS = 16                            # swimsim_route_n / swimsim_replica_census: n is 1..16
+RING_CHECKSUM_CHUNK = 1024                       # swimsim_ring_checksums: member indices the hash kernel expands per step
+EMPTY_RING_CHECKSUM = 3696677242                 # Fingerprint32(""): the ring checksum of a view without servers
 CENSUS_STATUSES = ("alive", "suspect", "faulty", "leave", "tombstone", "unknown")   # columns of a census count
 ERRORS = {-1: "EINVAL", -2: "ENOMEM", -3: "EHIP", -4: "ECAPACITY", -5: "ERANGE"}
 
@@ -195,6 +197,10 @@ def load_library(path: str = LIB_PATH):
         "swimsim_route_n": (C.c_int, [P, P, P, sz, u32, u32, P, sz, i32, P, P, C.POINTER(C.c_double)]),
         "swimsim_replica_census": (C.c_int, [P, P, P, sz, u32, u32, i32, i32, C.POINTER(u32), P, P, P, sz, C.POINTER(sz),
                                              C.POINTER(C.c_double)]),
+        "swimsim_ring_checksums": (C.c_int, [P, P, sz, i32, P, P, C.POINTER(u32), C.POINTER(C.c_double)]),
+        "swimsim_ring_census": (C.c_int, [P, i32, i32, C.POINTER(u32), P, P, P, P, sz, C.POINTER(sz), C.POINTER(u32),
+                                          C.POINTER(C.c_double)]),
+        "swimsim_ring_times": (C.c_int, [P, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     }
     for name, (res, args) in sigs.items():
         f = getattr(L, name)
@@ -298,6 +304,23 @@ def merge_route_histograms(parts):
     off = np.zeros(K + 1, np.uint64)
     off[1:] = np.cumsum(np.bincount(u >> 32, minlength=K))
     return counted, off, ((u & 0xFFFFFFFF) - 1).astype(np.int32), tot.astype(np.uint32), sum(p[4] for p in parts)
+
+
+def merge_ring_histograms(parts):
+    """add per-shard ring_census results (counted, hist_checksum, hist_count, hist_servers, hist_first, hashed, ms) per
+    checksum: the histogram of the union of the shards' rows, ascending by checksum. hist_first is the minimum over the
+    shards and hist_servers follows it; hashed and ms add."""
+    counted = sum(int(p[0]) for p in parts)
+    cs = np.concatenate([np.asarray(p[1], np.uint32) for p in parts])
+    cnt = np.concatenate([np.asarray(p[2], np.uint64) for p in parts])
+    srv = np.concatenate([np.asarray(p[3], np.uint32) for p in parts])
+    first = np.concatenate([np.asarray(p[4], np.uint32) for p in parts])
+    order = np.lexsort((first, cs))                                  # by checksum, then by first observer
+    cs, cnt, srv, first = cs[order], cnt[order], srv[order], first[order]
+    u, start = np.unique(cs, return_index=True)                      # (start: each checksum's lowest first observer)
+    tot = np.add.reduceat(cnt, start) if len(u) else np.zeros(0, np.uint64)
+    return (counted, u.astype(np.uint32), tot.astype(np.uint32), srv[start].astype(np.uint32),
+            first[start].astype(np.uint32), sum(int(p[5]) for p in parts), sum(p[6] for p in parts))
 
 
 def shard_range(n, nshards, rank):
@@ -706,6 +729,48 @@ class Cluster:
         return self._census_retry(load_library().swimsim_replica_census,
                                   (blob, off.ctypes.data, K, int(replica_points), n, w, int(mode)), max(1, 2 * n * K))
 
+    # ---- ring checksums through the observers' own ring views (swimsim_ring_checksums / swimsim_ring_census) ----
+    def ring_checksums(self, observers=None, mode=0):
+        """(checksums uint32 [nobs], servers uint32 [nobs], hashed, ms): Ringpop.Checksum() of observer observers[j], the
+        Fingerprint32 of the addresses its row holds alive or suspect joined by ";", and that view's server count.
+        observers (rows of this handle, duplicates allowed) = None means every owned row in order. mode 0 = equal views
+        share one hash chain, 1 = one chain per row, 2 = tests (identical results); hashed = the chains run."""
+        if observers is None:
+            ptr, n = None, self.nl
+        else:
+            obs = _member_list(observers)
+            ptr, n = (obs.ctypes.data if len(obs) else None), len(obs)
+        cs = np.empty(n, np.uint32)
+        srv = np.empty(n, np.uint32)
+        hashed, ms = C.c_uint32(), C.c_double()
+        self._chk(load_library().swimsim_ring_checksums(self.h, ptr, n, int(mode), cs.ctypes.data, srv.ctypes.data,
+                                                        C.byref(hashed), C.byref(ms)))
+        return cs, srv, hashed.value, ms.value
+
+    def ring_census(self, who="live", mode=0):
+        """(counted, hist_checksum, hist_count, hist_servers, hist_first, hashed, ms): one entry per distinct ring
+        checksum over the counted observer rows of this handle, ascending by checksum: the rows that answer it, that
+        view's server count and the lowest observer that answers it. The counts sum to counted
+        (swimsim.metrics.ring_agreement). who as for census(), mode as for ring_checksums()."""
+        w = _census_who(who, "ring_census")
+        cap = max(1, self.nl)                                        # (one entry per row at most: no second call)
+        while True:
+            cs, cnt, srv, first = (np.empty(cap, np.uint32) for _ in range(4))
+            counted, nh, hashed, ms = C.c_uint32(), C.c_size_t(), C.c_uint32(), C.c_double()
+            self._chk(load_library().swimsim_ring_census(self.h, w, int(mode), C.byref(counted), cs.ctypes.data,
+                                                         cnt.ctypes.data, srv.ctypes.data, first.ctypes.data, cap,
+                                                         C.byref(nh), C.byref(hashed), C.byref(ms)))
+            if nh.value <= cap:
+                k = nh.value
+                return counted.value, cs[:k].copy(), cnt[:k].copy(), srv[:k].copy(), first[:k].copy(), hashed.value, ms.value
+            cap = nh.value
+
+    def ring_times(self):
+        """(scan_ms, group_ms, hash_ms): the device time of the last ring_checksums / ring_census call, split"""
+        a, b, c = C.c_double(), C.c_double(), C.c_double()
+        self._chk(load_library().swimsim_ring_times(self.h, C.byref(a), C.byref(b), C.byref(c)))
+        return a.value, b.value, c.value
+
     def address(self, m):
         """member m's address (the synthetic one unless the cluster was given addresses)"""
         a = getattr(self, "_addresses", None)
@@ -1012,6 +1077,21 @@ class ShardedCluster:
         n = _replica_n(n, "replica_census")
         return merge_route_histograms([c.replica_census(keys, n, who, replica_points, mode) for c in self.shards])
 
+    def ring_checksums(self, observers=None, mode=0):
+        obs, parts = self._observer_shards(np.arange(self.n, dtype=np.uint32) if observers is None else observers,
+                                           "ring_checksums")
+        cs = np.empty(len(obs), np.uint32)
+        srv = np.empty(len(obs), np.uint32)
+        hashed, ms = 0, 0.0
+        for c, sel in parts:
+            cs[sel], srv[sel], hs, t = c.ring_checksums(obs[sel], mode)
+            hashed += hs
+            ms += t
+        return cs, srv, hashed, ms
+
+    def ring_census(self, who="live", mode=0):
+        return merge_ring_histograms([c.ring_census(who, mode) for c in self.shards])
+
     def address(self, m):
         return self.shards[0].address(m)
 
@@ -1223,3 +1303,7 @@ class Node:
         """the addresses of the (up to) n members this node holds responsible for `key`, in ring-walk order"""
         prefs, _ = self.c.route_n([key], [self.o], n, replica_points)
         return [self.c.address(int(m)) for m in prefs[0, 0] if m >= 0]
+
+    def Checksum(self):                                   # ringpop.go:571-577: the checksum of this node's own ring
+        """Fingerprint32 of the addresses this node holds alive or suspect, joined by ";" (hashring.go:100-107)"""
+        return int(self.c.ring_checksums([self.o])[0][0])

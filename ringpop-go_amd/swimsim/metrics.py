@@ -85,6 +85,31 @@ def route_agreement(counted, hist_off, hist_owner, hist_count) -> RouteAgreement
 
 
 @dataclass
+class RingAgreement:
+    """of a ring census (the ring.checksum gauge over the counted rows):
+    distinct:  the number of distinct ring checksums the counted rows answer (0: no row counted);
+    checksum:  the majority checksum, the lowest value among equals (None: no row counted);
+    share:     the fraction of the counted rows that answer it (0.0: no row counted);
+    all_agree: every counted row answers the same checksum (False when no row counted)."""
+    distinct: int
+    checksum: int | None
+    share: float
+    all_agree: bool
+
+
+def ring_agreement(counted, hist_checksum, hist_count) -> RingAgreement:
+    """counted, hist_checksum, hist_count as ring_census() returns them (checksums ascending, counts summing to counted)."""
+    cs = np.asarray(hist_checksum, dtype=np.int64).reshape(-1)
+    cnt = np.asarray(hist_count, dtype=np.int64).reshape(-1)
+    if len(cs) != len(cnt) or int(cnt.sum()) != int(counted) or (len(cs) > 1 and (np.diff(cs) <= 0).any()) or (cnt <= 0).any():
+        raise ValueError("ring_agreement: ascending distinct checksums with positive counts that sum to counted expected")
+    if not len(cs):
+        return RingAgreement(0, None, 0.0, False)
+    j = int(np.argmax(cnt))                                          # (argmax takes the first: the lowest checksum)
+    return RingAgreement(len(cs), int(cs[j]), float(cnt[j]) / float(counted), len(cs) == 1)
+
+
+@dataclass
 class ReplicaAgreement:
     """per key of a replica census with sets of n members:
     distinct:   the number of distinct members over the counted rows' replica sets;
