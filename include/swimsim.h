@@ -28,7 +28,9 @@
 extern "C" {
 #endif
 
-#define SWIMSIM_ABI_VERSION 15   /* 15: swimsim_ring_checksums, swimsim_ring_census and swimsim_ring_times (read-only; the
+#define SWIMSIM_ABI_VERSION 16   /* 16: swimsim_forward, swimsim_forward_census and swimsim_forward_times (read-only; the
+                                    results of every earlier call unchanged).
+                                    15: swimsim_ring_checksums, swimsim_ring_census and swimsim_ring_times (read-only; the
                                     results of every earlier call unchanged).
                                     14: swimsim_tuning.resp_echo and the unit "resp_echoed" (results unchanged).
                                     13: swimsim_pool_usage (a read-back; nothing else changed since 12). 12: the
@@ -517,6 +519,93 @@ int swimsim_ring_census(swimsim_t *h, int32_t who, int32_t mode, uint32_t *count
                         uint32_t *hist_count, uint32_t *hist_servers, uint32_t *hist_first, size_t cap, size_t *nhist,
                         uint32_t *hashed, double *ms);
 int swimsim_ring_times(swimsim_t *h, double *scan_ms, double *group_ms, double *hash_ms);
+
+/* ---- requests forwarded through every node's own ring view (ABI 16) ----
+ * A Ringpop node does not stop at Lookup. HandleOrForward (ringpop.go:687-712) handles a key itself when
+ * Lookup(key) == WhoAmI() and otherwise calls the owner through forward.Forwarder.ForwardRequest
+ * (forward/forwarder.go:156-174); that node runs HandleOrForward again, through its own ring. While the views disagree a
+ * request can die at a node that is gone, take extra hops, bounce between a node that has left and the nodes that have
+ * not heard yet, or be served by two nodes at once. These calls follow every request from node to node, on the device,
+ * for the state after the last round. They are read-only as the ABI 8-15 calls are: no state and no result of a round
+ * changes.
+ *
+ * owner(h, k) is the view-ring owner of ABI 9 (its deviation note applies unchanged);
+ * reach(a, b) = live(a) and live(b) and part(a) == part(b), as in docs/ROUND_SEMANTICS.md. A request for key k enters at
+ * node e with max_hops (1..64) forwards allowed:
+ *
+ *   if !live(e): ENTRY_DOWN, handler -1, hops 0
+ *   h = e, hops = 0
+ *   loop:
+ *     d = owner(h, k)
+ *     d == -1            -> NO_OWNER    (Lookup errs on an empty ring, ringpop.go:694-697)
+ *     d == h             -> hops == 0 ? LOCAL : DELIVERED; handler = h
+ *     hops == max_hops   -> HOP_LIMIT   (the request would need one forward more)
+ *     !reach(h, d)       -> UNREACHABLE (the forward call errs; holder = h, next = d)
+ *     h = d; hops += 1
+ *     policy ONE_HOP     -> DELIVERED, handler = h   (the forwarded header: a forwarded call is never forwarded again,
+ *                                                     forward/forwarder.go:176-201)
+ *
+ * Chains cannot loop while every holder holds itself alive or suspect: along a chain the clockwise distance from the
+ * key to the chosen point strictly falls, in (hash, member) order. (Node h forwards to d because d's point p is the
+ * first point >= the key among the servers of h's view. If d holds itself a server, p is a point of d's view too, so
+ * d's own choice is p or a point before it; d forwards on only when that point is strictly nearer the key.) A chain
+ * loops only through a node that is no server in its own ring, such as a node that has left and still runs.
+ * HOP_LIMIT therefore reports either a chain longer than max_hops or such a bounce.
+ *
+ * Retries are outside these calls. The reference retries over wall-clock time: MaxRetries is 3, after 3, 6 and 12 s,
+ * which is 15, 30 and 60 rounds at the default period, and AttemptRetry looks the key up again on each retry
+ * (forward/request_sender.go:206-243). UNREACHABLE is the outcome of one attempt. A caller models retries by stepping
+ * the cluster and asking again, with the holder as the entry node: that is why swimsim_forward takes arbitrary
+ * (entry, key) pairs.
+ *
+ * keys, off and replica_points are those of swimsim_route. policy: SWIMSIM_FWD_CHAIN = HandleOrForward at every hop,
+ * SWIMSIM_FWD_ONE_HOP = the first forward delivers.
+ *
+ * swimsim_forward: request i is key key_index[i] entering at node entry[i], nreq requests; duplicates are allowed.
+ * key_index = NULL: entry lists nreq / nkeys entry nodes (nreq must be a multiple of nkeys) and request j*nkeys + k is
+ * key k entering at entry[j]. outcome[i] and hops[i] (the forwards made) are required; handler[i] (the node that serves
+ * the request, -1 when none does), holder[i] (the node where the chain ended: the handler, the node whose call failed,
+ * the last holder, or the entry node) and next[i] (the destination that was not reached, for UNREACHABLE and HOP_LIMIT;
+ * otherwise -1) may each be NULL. The read-back is proportional to nreq; one host synchronisation per call.
+ *
+ * swimsim_forward_census: the entries are all rows whose observer is live; *counted = their number.
+ * outcomes[k*6 + c] counts the outcomes of key k and hops_hist[k*(max_hops+1) + j] the requests of key k that ended
+ * after j forwards; both sum to *counted per key. For key k, entries [hist_off[k], hist_off[k+1]) list every distinct
+ * handler, ascending, -1 first ("not served"), each with the number of entries whose request ends there; the counts of
+ * one key sum to *counted. A key is split when it has more than one handler >= 0. cap, *nhist (retry with larger
+ * buffers, no error) and the always-complete hist_off are those of swimsim_route_census, as are the pair buffers, the
+ * sort and the run count: the device stages only the (key, handler) pairs that differ from the handler under the first
+ * counted entry, so the result does not depend on arrival order and a cluster that agrees writes nothing; a pass whose
+ * pairs overflow is run again over fewer keys, never truncated. Host synchronisations per pass as for
+ * swimsim_route_census, and one more for the bins.
+ *
+ * mode: results are identical in every mode. 0 = production; 1 and 2 pass through to the route kernel's walk and direct
+ * path; 3 = tests only: the owner table holds 8 keys per pass, so small tests run several passes and a last partial
+ * one. ms (may be NULL) = the HIP-event time of the device work; swimsim_forward_times gives the last call's split
+ * over the owner table, the chases and (census) the rest: the keys' hashes, the pair sort and the run count.
+ *
+ * SWIMSIM_EINVAL, before any device work and with nothing written: every case of swimsim_route (NULL handle: -1);
+ * max_hops outside 1..64; an unknown policy or mode; an entry or key index out of range; nreq = 0, or no multiple of
+ * nkeys with key_index = NULL; a NULL required output; a handle that does not own every row: a chain may visit any
+ * row, and chains that cross shards are out of scope (the error text says so). SWIMSIM_ENOMEM leaves the handle usable.
+ *
+ * Memory, on first use and freed at destroy: the owner table of one pass, key-major, 4 bytes per row and key of the
+ * pass and at most 256 MiB (1,024 keys per pass at 65,536 rows); 22 bytes per request of one launch (at most 4 Mi
+ * requests); 4 * (7 + max_hops) bytes per key for the census's bins; the point table, the keys and the pair buffers are
+ * the ABI 9 buffers, shared. A handle that never calls these launches what it launched and keeps the swimsim_memory
+ * figures it had; swimsim_route and swimsim_route_census keep their kernels and results. */
+enum { SWIMSIM_FWD_LOCAL = 0, SWIMSIM_FWD_DELIVERED = 1, SWIMSIM_FWD_UNREACHABLE = 2, SWIMSIM_FWD_HOP_LIMIT = 3,
+       SWIMSIM_FWD_NO_OWNER = 4, SWIMSIM_FWD_ENTRY_DOWN = 5 };
+enum { SWIMSIM_FWD_CHAIN = 0, SWIMSIM_FWD_ONE_HOP = 1 };
+int swimsim_forward(swimsim_t *h, const uint8_t *keys, const uint64_t *off, size_t nkeys, uint32_t replica_points,
+                    const uint32_t *entry, const uint32_t *key_index, size_t nreq, uint32_t max_hops, int32_t policy,
+                    int32_t mode, uint8_t *outcome, uint8_t *hops, int32_t *handler, int32_t *holder, int32_t *next,
+                    double *ms);
+int swimsim_forward_census(swimsim_t *h, const uint8_t *keys, const uint64_t *off, size_t nkeys, uint32_t replica_points,
+                           uint32_t max_hops, int32_t policy, int32_t mode, uint32_t *counted, uint32_t *outcomes,
+                           uint32_t *hops_hist, uint64_t *hist_off, int32_t *hist_handler, uint32_t *hist_count,
+                           size_t cap, size_t *nhist, double *ms);
+int swimsim_forward_times(swimsim_t *h, double *table_ms, double *chase_ms, double *hist_ms);
 
 /* ---- measurement ---- */
 /* average device time (ms) of each kernel family since the last reset, for roofline reporting */

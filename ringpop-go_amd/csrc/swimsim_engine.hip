@@ -8,6 +8,7 @@
 #include "swimsim_xchg.hip"
 #include "swimsim_census.hip"
 #include "swimsim_route.hip"
+#include "swimsim_forward.hip"
 #include "swimsim_ringcs.hip"
 
 #include <hipcub/hipcub.hpp>
@@ -437,6 +438,16 @@ struct swimsim {
     size_t rc_cap = 0;
     bool rc_lds = false;
     double rc_split[3] = {0, 0, 0};
+    // forwarded requests (swimsim_forward / swimsim_forward_census, swimsim_forward.hip), allocated at the first call and
+    // kept until destroy: the owner table of one pass (key-major, fw_own_cap words), the requests of one launch and their
+    // five outputs (fw_req_cap each), the census's outcome and hop bins (fw_bins_cap words). The keys, the point table,
+    // the base handlers (rt_base) and the census's pair buffers are the route calls'; fw_split = the table / chase /
+    // histogram device times of the last call
+    int32_t *fw_own = nullptr, *fw_handler = nullptr, *fw_holder = nullptr, *fw_next = nullptr;
+    uint32_t *fw_ent = nullptr, *fw_key = nullptr, *fw_bins = nullptr;
+    uint8_t *fw_outcome = nullptr, *fw_hops = nullptr;
+    size_t fw_own_cap = 0, fw_req_cap = 0, fw_ent_cap = 0, fw_bins_cap = 0;
+    double fw_split[3] = {0, 0, 0};
     // reference-row checksum path (swimsim_checksum_ref.hip + swimsim_checksum_csr.hip), allocated at its first launch
     // (on for wide launches by default: the bench window runs 9.51 against 10.48 ms per round)
     int csr_mode = 1;                             // swimsim_tuning.cs_ref: 0 off, 1 wide launches, 2 every launch of

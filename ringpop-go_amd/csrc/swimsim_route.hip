@@ -29,7 +29,8 @@
 // The frame both kernels stand in: route_pick_row (the workgroup's row, or nothing to do), stages 1 and 2
 // (route_stage_bitmap, route_stage_list; route_goes_direct chooses the path), and in census mode route_stage_put (a
 // wave stages its exception pairs and flushes alone when full) and route_stage_finish (one cursor bump per workgroup).
-// Only the search of one key differs.
+// Only the search of one key differs: route_owner is k_route's, and k_fwd_table (swimsim_forward.hip) runs
+// it in the same frame to fill its key-major owner table.
 // The kernels only read mw and live, on the main stream (as the census).
 #pragma once
 #include "swimsim_device.h"
@@ -257,6 +258,33 @@ __device__ __forceinline__ void route_stage_list(const DS &d, const unsigned lon
     __syncthreads();
 }
 
+// Stage 3, one thread: the owner of key k in a row of cnt > 0 servers, by the path stages 1 and 2 prepared. Every lane of
+// a wave that takes the direct path is at the same list index (the readfirstlane below).
+__device__ __forceinline__ int32_t route_owner(const RouteArgs &a, const unsigned long long *route_bm, const uint32_t *list,
+                                               uint32_t cnt, bool direct, uint32_t k) {
+    const uint32_t h = a.kh[k];
+    if (direct) {
+        unsigned long long best = ~0ull;
+        for (uint32_t j = 0; j < cnt; j++) {
+            const uint32_t m = (uint32_t)__builtin_amdgcn_readfirstlane((int)list[j]);
+            const uint32_t *hp = a.hm + (size_t)m * a.R;
+            for (uint32_t i = 0; i < a.R; i++) {
+                const unsigned long long v = ((unsigned long long)(hp[i] - h) << 32) | m;
+                best = v < best ? v : best;
+            }
+        }
+        return (int32_t)(uint32_t)best;
+    }
+    const uint32_t *ptm = reinterpret_cast<const uint32_t *>(a.pts);   // (the member is the low word of a point)
+    uint32_t p = a.p0[k];
+    for (uint32_t step = 0; step < a.P; step++, p++) {                 // cnt > 0: a present member's point is met
+        if (p >= a.P) p = 0;
+        const uint32_t m = ptm[2 * (size_t)p];
+        if (route_present(route_bm, m)) return (int32_t)m;
+    }
+    return -1;
+}
+
 // route: grid = routed rows; census: grid = NL (workgroups of rows that do not count return at once).
 // Dynamic LDS: route_bitmap_bytes(NP).
 template <bool CENSUS>
@@ -279,33 +307,10 @@ __global__ void __launch_bounds__(ROUTE_THREADS) k_route(DS d, RouteArgs a) {
     // ---- 3. one thread per key ----
     const unsigned long long below = (1ull << lane) - 1ull;
     uint32_t nx = 0;                                                   // census: pairs staged by this wave (wave-uniform)
-    const uint32_t *ptm = reinterpret_cast<const uint32_t *>(a.pts);   // (the member is the low word of a point)
     for (uint32_t kb = a.k0; kb < a.k1; kb += ROUTE_THREADS) {         // (kb + tid < 2^32: k1 <= 2^31)
         const uint32_t k = kb + tid;
         const bool valid = k < a.k1;
-        int32_t own = -1;
-        if (valid && cnt) {
-            const uint32_t h = a.kh[k];
-            if (direct) {
-                unsigned long long best = ~0ull;
-                for (uint32_t j = 0; j < cnt; j++) {
-                    const uint32_t m = (uint32_t)__builtin_amdgcn_readfirstlane((int)list[j]);
-                    const uint32_t *hp = a.hm + (size_t)m * a.R;
-                    for (uint32_t i = 0; i < a.R; i++) {
-                        const unsigned long long v = ((unsigned long long)(hp[i] - h) << 32) | m;
-                        best = v < best ? v : best;
-                    }
-                }
-                own = (int32_t)(uint32_t)best;
-            } else {
-                uint32_t p = a.p0[k];
-                for (uint32_t step = 0; step < a.P; step++, p++) {     // cnt > 0: a present member's point is met
-                    if (p >= a.P) p = 0;
-                    const uint32_t m = ptm[2 * (size_t)p];
-                    if (route_present(route_bm, m)) { own = (int32_t)m; break; }
-                }
-            }
-        }
+        const int32_t own = valid && cnt ? route_owner(a, route_bm, list, cnt, direct, k) : -1;
         if (!CENSUS) {
             if (valid) a.owners[(size_t)blockIdx.x * a.K + k] = own;
         } else {                                                       // (every lane is here: one put per key step)

@@ -1,5 +1,6 @@
 // swimsim_route_host.hip — the host side of key routing and replica sets: swimsim_route, swimsim_route_census,
-// swimsim_route_n and swimsim_replica_census (kernels: swimsim_route.hip), and of the ring
+// swimsim_route_n and swimsim_replica_census (kernels: swimsim_route.hip), of forwarded requests:
+// swimsim_forward and swimsim_forward_census (kernels: swimsim_forward.hip), and of the ring
 // checksums: swimsim_ring_checksums and swimsim_ring_census (kernels: swimsim_ringcs.hip). Part of
 // swimsim_engine.hip, which includes it after struct swimsim and the helpers it uses (dalloc, stream_sync, DeviceScope).
 
@@ -266,15 +267,17 @@ void route_census_args(swimsim *h, RouteArgs *a, uint32_t first, uint32_t all) {
 // a pass that fits are sorted and run-length encoded, and for every key k of the pass emit(k, runs, rcnt, i0, i1, put)
 // turns its runs [i0, i1) (ascending) into histogram entries through put(member, count), which writes the first cap
 // entries and counts all of them. The first pass's time includes the keys and the base, which the caller has enqueued.
+// first_chunk (0: all keys) bounds the keys of a pass from the start, for a caller whose pass has scratch per key.
 extern "C++" template <typename Launch, typename Emit, typename OneKeyError>
 int route_census_passes(swimsim *h, size_t nkeys, Launch launch, Emit emit, OneKeyError one_key_error, uint64_t *hist_off,
-                        int32_t *hist_member, uint32_t *hist_count, size_t cap, size_t *nhist, double *ms) {
+                        int32_t *hist_member, uint32_t *hist_count, size_t cap, size_t *nhist, double *ms,
+                        size_t first_chunk = 0) {
     double total_ms = 0;
     float t = 0;
     uint32_t *nruns_d = reinterpret_cast<uint32_t *>(h->rt_cur + 1);
     std::vector<unsigned long long> runs;
     std::vector<uint32_t> rcnt;
-    size_t total = 0, kb = 0, chunk = nkeys;
+    size_t total = 0, kb = 0, chunk = first_chunk ? std::min(first_chunk, nkeys) : nkeys;
     bool first_pass = true;
     auto put = [&](int32_t member, uint32_t c) {
         if (total < cap) {
@@ -344,6 +347,28 @@ int route_census_passes(swimsim *h, size_t nkeys, Launch launch, Emit emit, OneK
     return SWIMSIM_OK;
 }
 
+// The emit of a census whose pairs are key << 32 | answer + 1, one answer (an owner, a handler; -1: none) per counted
+// row and key: the runs of key k are ascending by answer + 1, and base[k], the answer under the first counted row,
+// takes the rows that no run counts.
+extern "C++" inline auto route_emit_answers(const std::vector<int32_t> &base, uint32_t ncount) {
+    return [&base, ncount](size_t k, const std::vector<unsigned long long> &runs, const std::vector<uint32_t> &rcnt, size_t i0,
+                           size_t i1, auto put) {
+        uint64_t exc = 0;
+        for (size_t j = i0; j < i1; j++) exc += rcnt[j];
+        const uint32_t bo = (uint32_t)(base[k] + 1), bc = (uint32_t)(ncount - exc);
+        bool placed = bc == 0;
+        for (size_t i = i0; i < i1; i++) {
+            const uint32_t o1 = (uint32_t)runs[i];
+            if (!placed && bo < o1) {
+                put(base[k], bc);
+                placed = true;
+            }
+            put((int32_t)o1 - 1, rcnt[i]);
+        }
+        if (!placed) put(base[k], bc);
+    };
+}
+
 }  // namespace
 
 int swimsim_route(swimsim_t *h, const uint8_t *keys, const uint64_t *off, size_t nkeys, uint32_t replica_points,
@@ -404,27 +429,11 @@ int swimsim_route_census(swimsim_t *h, const uint8_t *keys, const uint64_t *off,
         a.k1 = k1;
         hipLaunchKernelGGL(k_route<true>, dim3(h->NL), dim3(ROUTE_THREADS), route_bitmap_bytes(h->NP), h->s, h->d, a);
     };
-    // the runs of key k are ascending by owner + 1; the base owner takes the rows that no run counts
-    auto emit = [&](size_t k, const std::vector<unsigned long long> &runs, const std::vector<uint32_t> &rcnt, size_t i0, size_t i1,
-                    auto put) {
-        uint64_t exc = 0;
-        for (size_t j = i0; j < i1; j++) exc += rcnt[j];
-        const uint32_t bo = (uint32_t)(base[k] + 1), bc = (uint32_t)(ncount - exc);
-        bool placed = bc == 0;
-        for (size_t i = i0; i < i1; i++) {
-            const uint32_t o1 = (uint32_t)runs[i];
-            if (!placed && bo < o1) {
-                put(base[k], bc);
-                placed = true;
-            }
-            put((int32_t)o1 - 1, rcnt[i]);
-        }
-        if (!placed) put(base[k], bc);
-    };
     auto one_key_error = [&](unsigned long long cur) {
         return h->fail(SWIMSIM_EHIP, "route census: %llu exceptions of one key over %u rows", cur, h->NL);
     };
-    return route_census_passes(h, nkeys, launch, emit, one_key_error, hist_off, hist_owner, hist_count, cap, nhist, ms);
+    return route_census_passes(h, nkeys, launch, route_emit_answers(base, ncount), one_key_error, hist_off, hist_owner,
+                               hist_count, cap, nhist, ms);
 }
 
 // ---- replica sets through the observers' ring views (k_route_n) ----
@@ -540,6 +549,287 @@ int swimsim_replica_census(swimsim_t *h, const uint8_t *keys, const uint64_t *of
         return h->fail(SWIMSIM_EHIP, "replica census: %llu exceptions of one key over %u rows, n = %u", cur, h->NL, n);
     };
     return route_census_passes(h, nkeys, launch, emit, one_key_error, hist_off, hist_member, hist_count, cap, nhist, ms);
+}
+
+// ---- requests forwarded through the observers' ring views (swimsim_forward.hip) ----
+namespace {
+
+constexpr size_t FWD_OWN_WORDS = (size_t)64 << 20;       // the owner table of one pass at most (256 MiB): 1,024 keys at 65,536 rows
+constexpr size_t FWD_REQ_SLICE = (size_t)4 << 20;        // requests of one listed launch at most (22 B each on the device)
+constexpr size_t FWD_TEST_CHUNK = 8;                     // mode 3 (tests): keys per pass
+
+// the HIP events of a call's passes, three per pass (before the table, after it, after the chases); destroyed with the call
+struct FwdEvents {
+    std::vector<hipEvent_t> ev;
+    ~FwdEvents() {
+        for (hipEvent_t e : ev) hipEventDestroy(e);
+    }
+    hipError_t mark(hipStream_t s) {
+        hipEvent_t e = nullptr;
+        hipError_t rc = hipEventCreate(&e);
+        if (rc != hipSuccess) return rc;
+        ev.push_back(e);
+        return hipEventRecord(e, s);
+    }
+    // after the stream is synchronised: the passes' table and chase times
+    hipError_t split(double *table_ms, double *chase_ms) const {
+        *table_ms = *chase_ms = 0;
+        for (size_t i = 0; i + 2 < ev.size(); i += 3) {
+            float a = 0, b = 0;
+            hipError_t rc = hipEventElapsedTime(&a, ev[i], ev[i + 1]);
+            if (rc == hipSuccess) rc = hipEventElapsedTime(&b, ev[i + 1], ev[i + 2]);
+            if (rc != hipSuccess) return rc;
+            *table_ms += a;
+            *chase_ms += b;
+        }
+        return hipSuccess;
+    }
+};
+
+// what both entry points refuse before any device work, beyond the output pointers; *chunk = the keys of a pass
+int fwd_check(swimsim *h, const uint8_t *keys, const uint64_t *off, size_t nkeys, uint32_t R, uint32_t max_hops, int32_t policy,
+              int32_t mode, const char *who, size_t *chunk) {
+    if (mode < 0 || mode > 3) return h->fail(SWIMSIM_EINVAL, "%s: unknown mode %d", who, mode);
+    if (int rc = route_check(h, keys, off, nkeys, R, mode == 3 ? 0 : mode, who)) return rc;
+    if (max_hops < 1 || max_hops > FWD_HOPS_MAX) return h->fail(SWIMSIM_EINVAL, "%s: max_hops %u not in 1..%u", who, max_hops, FWD_HOPS_MAX);
+    if (policy != SWIMSIM_FWD_CHAIN && policy != SWIMSIM_FWD_ONE_HOP) return h->fail(SWIMSIM_EINVAL, "%s: unknown policy %d", who, policy);
+    if (h->NL != h->N)
+        return h->fail(SWIMSIM_EINVAL, "%s: this handle holds rows %u..%u of %u; a chain may visit any row, and chains that cross "
+                       "shards are not supported", who, h->lo, h->lo + h->NL, h->N);
+    *chunk = std::min(nkeys, mode == 3 ? FWD_TEST_CHUNK : std::max<size_t>(1, FWD_OWN_WORDS / h->N));
+    return 0;
+}
+
+// the owner table of `chunk` keys, on first use (exactly chunk * N words: the table is the call's largest buffer)
+int fwd_table_scratch(swimsim *h, size_t chunk) {
+    const size_t need = chunk * h->N;
+    if (need > h->fw_own_cap) {
+        if (h->fw_own) HIPCHK(h, stream_sync(h));
+        dfree(h, &h->fw_own, dalloc_bytes(h->fw_own_cap, 4));
+        h->fw_own_cap = 0;
+        if (int rc = dalloc(h, &h->fw_own, need, "forward owner table")) return rc;
+        h->fw_own_cap = need;
+    }
+    return route_allow_lds(h, 4096, &k_fwd_table, &k_fwd_table);     // (N above ~491,000)
+}
+
+// the table of keys [k0, k1): own[(k - k0) * N + row] for every live row
+void fwd_table(swimsim *h, const swimsim::RouteTable *tab, size_t nkeys, int32_t mode, uint32_t k0, uint32_t k1) {
+    RouteArgs a = route_args(h, tab, nkeys, mode == 3 ? 0 : mode);
+    a.k0 = k0;
+    a.k1 = k1;
+    a.owners = h->fw_own;
+    hipLaunchKernelGGL(k_fwd_table, dim3(h->N), dim3(ROUTE_THREADS), route_bitmap_bytes(h->NP), h->s, h->d, a);
+}
+
+FwdArgs fwd_args(swimsim *h, uint32_t k0, uint32_t k1, uint32_t max_hops, int32_t policy) {
+    FwdArgs f{};
+    f.own = h->fw_own;
+    f.k0 = k0; f.k1 = k1;
+    f.max_hops = max_hops;
+    f.one_hop = policy == SWIMSIM_FWD_ONE_HOP;
+    return f;
+}
+
+}  // namespace
+
+int swimsim_forward(swimsim_t *h, const uint8_t *keys, const uint64_t *off, size_t nkeys, uint32_t replica_points,
+                    const uint32_t *entry, const uint32_t *key_index, size_t nreq, uint32_t max_hops, int32_t policy, int32_t mode,
+                    uint8_t *outcome, uint8_t *hops, int32_t *handler, int32_t *holder, int32_t *next, double *ms) {
+    if (!h) return SWIMSIM_EINVAL;
+    if (!outcome || !hops) return h->fail(SWIMSIM_EINVAL, "forward: no output buffer");
+    size_t chunk = 0;
+    if (int rc = fwd_check(h, keys, off, nkeys, replica_points, max_hops, policy, mode, "forward", &chunk)) return rc;
+    if (!entry || nreq == 0) return h->fail(SWIMSIM_EINVAL, "forward: no requests");
+    if (!key_index && nreq % nkeys) return h->fail(SWIMSIM_EINVAL, "forward: %zu requests are no multiple of %zu keys", nreq, nkeys);
+    const size_t nent = key_index ? nreq : nreq / nkeys;             // the entries listed
+    for (size_t i = 0; i < nent; i++)
+        if (entry[i] >= h->N) return h->fail(SWIMSIM_EINVAL, "forward: entry node %u out of range", entry[i]);
+    // the requests in key order, so that a pass finds its own in one piece and a wave's lanes share a column:
+    // start[k] = the first request of key k; with key_index, order[] lists the requests (stable within a key)
+    std::vector<uint64_t> start(nkeys + 1, 0);
+    std::vector<uint32_t> sent, skey;
+    std::vector<size_t> order;
+    if (key_index) {
+        for (size_t i = 0; i < nreq; i++) {
+            if (key_index[i] >= nkeys) return h->fail(SWIMSIM_EINVAL, "forward: key index %u out of range", key_index[i]);
+            start[key_index[i] + 1]++;
+        }
+        for (size_t k = 0; k < nkeys; k++) start[k + 1] += start[k];
+        std::vector<uint64_t> at(start.begin(), start.end() - 1);
+        order.resize(nreq); sent.resize(nreq); skey.resize(nreq);
+        for (size_t i = 0; i < nreq; i++) {
+            const size_t p = at[key_index[i]]++;
+            order[p] = i; sent[p] = entry[i]; skey[p] = key_index[i];
+        }
+    } else {
+        for (size_t k = 0; k <= nkeys; k++) start[k] = (uint64_t)k * nent;
+    }
+    DeviceScope ds(h->device);
+    const size_t slice = std::min(nreq, FWD_REQ_SLICE);
+    const swimsim::RouteTable *tab = nullptr;
+    int rc = 0;
+    if ((rc = fwd_table_scratch(h, chunk)) ||
+        (rc = route_grow(h, &h->fw_ent, &h->fw_ent_cap, key_index ? slice : nent, "forward entries")))
+        return rc;
+    if (slice > h->fw_req_cap) {                                     // the requests' keys and outputs, one capacity
+        if (h->fw_key) HIPCHK(h, stream_sync(h));
+        const size_t o = h->fw_req_cap;
+        auto drop = [&](size_t c) {
+            dfree(h, &h->fw_key, dalloc_bytes(c, 4));
+            dfree(h, &h->fw_outcome, dalloc_bytes(c, 1));
+            dfree(h, &h->fw_hops, dalloc_bytes(c, 1));
+            dfree(h, &h->fw_handler, dalloc_bytes(c, 4));
+            dfree(h, &h->fw_holder, dalloc_bytes(c, 4));
+            dfree(h, &h->fw_next, dalloc_bytes(c, 4));
+        };
+        drop(o);
+        h->fw_req_cap = 0;
+        const size_t c = std::min(FWD_REQ_SLICE, slice + slice / 2);
+        if ((rc = dalloc(h, &h->fw_key, c, "forward key indices")) || (rc = dalloc(h, &h->fw_outcome, c, "forward outcomes")) ||
+            (rc = dalloc(h, &h->fw_hops, c, "forward hops")) || (rc = dalloc(h, &h->fw_handler, c, "forward handlers")) ||
+            (rc = dalloc(h, &h->fw_holder, c, "forward holders")) || (rc = dalloc(h, &h->fw_next, c, "forward destinations"))) {
+            drop(c);                                                 // (a buffer that was not allocated is skipped)
+            return rc;
+        }
+        h->fw_req_cap = c;
+    }
+    if ((rc = route_keys(h, keys, off, nkeys, replica_points, &tab))) return rc;
+    if (!key_index) HIPCHK(h, hipMemcpyAsync(h->fw_ent, entry, nent * 4, hipMemcpyHostToDevice, h->s));
+    // the outputs in key order; they reach the caller's buffers only when the call has succeeded
+    std::vector<uint8_t> o_out(nreq), o_hops(nreq);
+    std::vector<int32_t> o_handler(handler ? nreq : 0), o_holder(holder ? nreq : 0), o_next(next ? nreq : 0);
+    FwdEvents evs;
+    for (size_t kb = 0; kb < nkeys; kb += chunk) {
+        const size_t ke = std::min(nkeys, kb + chunk);
+        HIPCHK(h, evs.mark(h->s));
+        fwd_table(h, tab, nkeys, mode, (uint32_t)kb, (uint32_t)ke);
+        HIPCHK(h, evs.mark(h->s));
+        FwdArgs f = fwd_args(h, (uint32_t)kb, (uint32_t)ke, max_hops, policy);
+        f.ent = h->fw_ent;
+        f.key = key_index ? h->fw_key : nullptr;
+        f.nent = (uint32_t)nent;
+        f.outcome = h->fw_outcome; f.hops = h->fw_hops;
+        f.handler = h->fw_handler; f.holder = h->fw_holder; f.next = h->fw_next;
+        for (uint64_t r0 = start[kb]; r0 < start[ke]; r0 += slice) {
+            const size_t nr = (size_t)std::min<uint64_t>(slice, start[ke] - r0);
+            if (key_index) {
+                HIPCHK(h, hipMemcpyAsync(h->fw_ent, sent.data() + r0, nr * 4, hipMemcpyHostToDevice, h->s));
+                HIPCHK(h, hipMemcpyAsync(h->fw_key, skey.data() + r0, nr * 4, hipMemcpyHostToDevice, h->s));
+            }
+            f.at = r0 - start[kb];
+            f.nreq = (uint32_t)nr;
+            hipLaunchKernelGGL(k_fwd_chase<false>, dim3(blocks_for_threads((uint32_t)nr)), dim3(FWD_THREADS), 0, h->s, h->d, f);
+            HIPCHK(h, hipMemcpyAsync(o_out.data() + r0, h->fw_outcome, nr, hipMemcpyDeviceToHost, h->s));
+            HIPCHK(h, hipMemcpyAsync(o_hops.data() + r0, h->fw_hops, nr, hipMemcpyDeviceToHost, h->s));
+            if (handler) HIPCHK(h, hipMemcpyAsync(o_handler.data() + r0, h->fw_handler, nr * 4, hipMemcpyDeviceToHost, h->s));
+            if (holder) HIPCHK(h, hipMemcpyAsync(o_holder.data() + r0, h->fw_holder, nr * 4, hipMemcpyDeviceToHost, h->s));
+            if (next) HIPCHK(h, hipMemcpyAsync(o_next.data() + r0, h->fw_next, nr * 4, hipMemcpyDeviceToHost, h->s));
+        }
+        HIPCHK(h, evs.mark(h->s));
+    }
+    HIPCHK(h, hipEventRecord(h->rt_ev[1], h->s));
+    HIPCHK(h, stream_sync(h));                                       // the call's one host synchronisation
+    HIPCHK(h, hipGetLastError());
+    float t = 0;
+    HIPCHK(h, hipEventElapsedTime(&t, h->rt_ev[0], h->rt_ev[1]));
+    HIPCHK(h, evs.split(&h->fw_split[0], &h->fw_split[1]));
+    h->fw_split[2] = 0;
+    // key order back to request order: request j * nkeys + k sits at k * nent + j, a listed request i at order[] = i
+    auto slot = [&](size_t p) { return key_index ? order[p] : (p % nent) * nkeys + p / nent; };
+    for (size_t p = 0; p < nreq; p++) {
+        const size_t i = slot(p);
+        outcome[i] = o_out[p];
+        hops[i] = o_hops[p];
+        if (handler) handler[i] = o_handler[p];
+        if (holder) holder[i] = o_holder[p];
+        if (next) next[i] = o_next[p];
+    }
+    if (ms) *ms = t;
+    return SWIMSIM_OK;
+}
+
+int swimsim_forward_census(swimsim_t *h, const uint8_t *keys, const uint64_t *off, size_t nkeys, uint32_t replica_points,
+                           uint32_t max_hops, int32_t policy, int32_t mode, uint32_t *counted, uint32_t *outcomes,
+                           uint32_t *hops_hist, uint64_t *hist_off, int32_t *hist_handler, uint32_t *hist_count, size_t cap,
+                           size_t *nhist, double *ms) {
+    if (!h) return SWIMSIM_EINVAL;
+    if (!counted || !outcomes || !hops_hist || !hist_off || !nhist || (cap && (!hist_handler || !hist_count)))
+        return h->fail(SWIMSIM_EINVAL, "forward census: no output buffer");
+    size_t chunk = 0;
+    if (int rc = fwd_check(h, keys, off, nkeys, replica_points, max_hops, policy, mode, "forward census", &chunk)) return rc;
+    const size_t nbin = nkeys * FWD_NOUT, nhop = nkeys * (max_hops + 1);
+    uint32_t all = 0, first = SRC_NONE;
+    if (int rc = route_counted(h, SWIMSIM_CENSUS_LIVE, "forward census", nkeys, &all, &first, counted, hist_off, nhist, ms)) return rc;
+    const uint32_t ncount = *counted;
+    h->fw_split[0] = h->fw_split[1] = h->fw_split[2] = 0;
+    if (ncount == 0) {                                               // no entry: every bin is zero
+        memset(outcomes, 0, nbin * 4);
+        memset(hops_hist, 0, nhop * 4);
+        return SWIMSIM_OK;
+    }
+    DeviceScope ds(h->device);
+    // a pass over one key appends at most one pair per row, so a buffer of at least NL pairs always ends the chunking
+    const swimsim::RouteTable *tab = nullptr;
+    int rc = 0;
+    if ((rc = route_exc_scratch(h, h->NL)) || (rc = fwd_table_scratch(h, chunk)) ||
+        (rc = route_grow(h, &h->fw_ent, &h->fw_ent_cap, 1, "forward entries")) ||
+        (rc = route_grow(h, &h->fw_bins, &h->fw_bins_cap, nbin + nhop, "forward bins")) ||
+        (rc = route_keys(h, keys, off, nkeys, replica_points, &tab)))
+        return rc;
+    uint32_t *d_out = h->fw_bins, *d_hop = h->fw_bins + nbin;
+    HIPCHK(h, hipMemcpyAsync(h->fw_ent, &first, 4, hipMemcpyHostToDevice, h->s));
+    std::vector<int32_t> base(nkeys);
+    FwdEvents evs;
+    hipError_t lerr = hipSuccess;
+    // a pass: the table of its keys, the base handlers (the chain from the first counted entry), its bins zeroed (a
+    // pass that overflows is run again), the chases of every live row
+    auto launch = [&](uint32_t k0, uint32_t k1) {
+        auto ok = [&](hipError_t e) { if (lerr == hipSuccess) lerr = e; };
+        ok(evs.mark(h->s));
+        fwd_table(h, tab, nkeys, mode, k0, k1);
+        ok(evs.mark(h->s));
+        FwdArgs f = fwd_args(h, k0, k1, max_hops, policy);
+        f.ent = h->fw_ent;
+        f.nent = 1;
+        f.nreq = k1 - k0;
+        f.handler = h->rt_base + k0;
+        hipLaunchKernelGGL(k_fwd_chase<false>, dim3(blocks_for_threads(k1 - k0)), dim3(FWD_THREADS), 0, h->s, h->d, f);
+        ok(hipMemcpyAsync(base.data() + k0, h->rt_base + k0, (size_t)(k1 - k0) * 4, hipMemcpyDeviceToHost, h->s));
+        ok(hipMemsetAsync(d_out + (size_t)k0 * FWD_NOUT, 0, (size_t)(k1 - k0) * FWD_NOUT * 4, h->s));
+        ok(hipMemsetAsync(d_hop + (size_t)k0 * (max_hops + 1), 0, (size_t)(k1 - k0) * (max_hops + 1) * 4, h->s));
+        f.handler = nullptr;
+        f.base = h->rt_base;
+        f.outcomes = d_out;
+        f.hops_hist = d_hop;
+        route_census_args(h, &f.r, first, all);
+        const uint32_t nblk = (h->N + FWD_THREADS - 1) / FWD_THREADS;
+        hipLaunchKernelGGL(k_fwd_chase<true>, dim3((k1 - k0) * nblk), dim3(FWD_THREADS), 0, h->s, h->d, f);
+        ok(evs.mark(h->s));
+    };
+    auto one_key_error = [&](unsigned long long cur) {
+        return h->fail(SWIMSIM_EHIP, "forward census: %llu exceptions of one key over %u rows", cur, h->NL);
+    };
+    double total = 0;
+    rc = route_census_passes(h, nkeys, launch, route_emit_answers(base, ncount), one_key_error, hist_off, hist_handler, hist_count,
+                             cap, nhist, &total, chunk);
+    if (rc) return rc;
+    HIPCHK(h, lerr);
+    HIPCHK(h, hipMemcpyAsync(outcomes, d_out, nbin * 4, hipMemcpyDeviceToHost, h->s));
+    HIPCHK(h, hipMemcpyAsync(hops_hist, d_hop, nhop * 4, hipMemcpyDeviceToHost, h->s));
+    HIPCHK(h, stream_sync(h));
+    HIPCHK(h, evs.split(&h->fw_split[0], &h->fw_split[1]));
+    h->fw_split[2] = std::max(0.0, total - h->fw_split[0] - h->fw_split[1]);
+    if (ms) *ms = total;
+    return SWIMSIM_OK;
+}
+
+int swimsim_forward_times(swimsim_t *h, double *table_ms, double *chase_ms, double *hist_ms) {
+    if (!h || !table_ms || !chase_ms || !hist_ms) return SWIMSIM_EINVAL;
+    *table_ms = h->fw_split[0];
+    *chase_ms = h->fw_split[1];
+    *hist_ms = h->fw_split[2];
+    return SWIMSIM_OK;
 }
 
 // ---- ring checksums through the observers' ring views (swimsim_ringcs.hip) ----

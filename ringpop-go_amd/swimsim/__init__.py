@@ -39,6 +39,11 @@ CENSUS_WHO = {"live": CENSUS_LIVE, "all": CENSUS_ALL}
 ROUTE_N_REPLICAS = 16                            # swimsim_route_n / swimsim_replica_census: n is 1..16
 RING_CHECKSUM_CHUNK = 1024                       # swimsim_ring_checksums: member indices the hash kernel expands per step
 EMPTY_RING_CHECKSUM = 3696677242                 # Fingerprint32(""): the ring checksum of a view without servers
+FWD_LOCAL, FWD_DELIVERED, FWD_UNREACHABLE, FWD_HOP_LIMIT, FWD_NO_OWNER, FWD_ENTRY_DOWN = range(6)   # swimsim_forward outcomes
+FWD_OUTCOMES = ("local", "delivered", "unreachable", "hop_limit", "no_owner", "entry_down")
+FWD_CHAIN, FWD_ONE_HOP = 0, 1                    # swimsim_forward `policy`
+FWD_POLICY = {"chain": FWD_CHAIN, "one_hop": FWD_ONE_HOP}
+FWD_MAX_HOPS = 64                                # swimsim_forward: max_hops is 1..64
 CENSUS_STATUSES = ("alive", "suspect", "faulty", "leave", "tombstone", "unknown")   # columns of a census count
 ERRORS = {-1: "EINVAL", -2: "ENOMEM", -3: "EHIP", -4: "ECAPACITY", -5: "ERANGE"}
 
@@ -201,6 +206,10 @@ def load_library(path: str = LIB_PATH):
         "swimsim_ring_census": (C.c_int, [P, i32, i32, C.POINTER(u32), P, P, P, P, sz, C.POINTER(sz), C.POINTER(u32),
                                           C.POINTER(C.c_double)]),
         "swimsim_ring_times": (C.c_int, [P, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+        "swimsim_forward": (C.c_int, [P, P, P, sz, u32, P, P, sz, u32, i32, i32, P, P, P, P, P, C.POINTER(C.c_double)]),
+        "swimsim_forward_census": (C.c_int, [P, P, P, sz, u32, u32, i32, i32, C.POINTER(u32), P, P, P, P, P, sz,
+                                             C.POINTER(sz), C.POINTER(C.c_double)]),
+        "swimsim_forward_times": (C.c_int, [P, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     }
     for name, (res, args) in sigs.items():
         f = getattr(L, name)
@@ -284,6 +293,13 @@ def _replica_n(n, what):
     if isinstance(n, bool) or int(n) != n or not 1 <= int(n) <= ROUTE_N_REPLICAS:
         raise ValueError(f"{what}: n is 1..{ROUTE_N_REPLICAS}, not {n!r}")
     return int(n)
+
+
+def _forward_policy(policy, what):
+    p = FWD_POLICY.get(policy, policy) if isinstance(policy, str) else policy
+    if isinstance(p, str):
+        raise ValueError(f"{what}: policy is 'chain' or 'one_hop', not {policy!r}")
+    return int(p)
 
 
 def merge_route_histograms(parts):
@@ -771,6 +787,69 @@ class Cluster:
         self._chk(load_library().swimsim_ring_times(self.h, C.byref(a), C.byref(b), C.byref(c)))
         return a.value, b.value, c.value
 
+    # ---- requests forwarded through the observers' own ring views (swimsim_forward / swimsim_forward_census) ----
+    def forward(self, keys, entries, key_index=None, max_hops=8, policy="chain", replica_points=100, mode=0):
+        """(outcome uint8, hops uint8, handler, holder, next int32, ms) of requests followed from node to node through
+        every node's own ring view (Ringpop.HandleOrForward): a node handles a key it owns by its own view and forwards
+        it to the owner otherwise, at most max_hops (1..64) times. With key_index, request i is key keys[key_index[i]]
+        entering at node entries[i] (arrays of [nreq]); without, every key enters at every listed entry and the arrays are
+        [len(entries), K]. outcome is one of FWD_OUTCOMES; handler = the node that serves the request or -1; holder = the
+        node where the chain ended; next = the destination not reached (unreachable, hop_limit) or -1. policy "chain" =
+        HandleOrForward at every hop, "one_hop" = the first forward delivers. The handle must own every row."""
+        pol = _forward_policy(policy, "forward")
+        blob, off = _pack_keys(keys)
+        K = len(off) - 1
+        ent = _member_list(entries)
+        if key_index is None:
+            kix, shape = None, (len(ent), K)
+        else:
+            kix = _member_list(key_index)
+            if len(kix) != len(ent):
+                raise ValueError(f"forward: {len(ent)} entries for {len(kix)} key indices")
+            shape = (len(ent),)
+        nreq = int(np.prod(shape))
+        outcome, hops = np.empty(shape, np.uint8), np.empty(shape, np.uint8)
+        handler, holder, nxt = (np.empty(shape, np.int32) for _ in range(3))
+        ms = C.c_double()
+        self._chk(load_library().swimsim_forward(self.h, blob, off.ctypes.data, K, int(replica_points),
+                                                 ent.ctypes.data if len(ent) else None,
+                                                 kix.ctypes.data if kix is not None and len(kix) else None, nreq,
+                                                 int(max_hops), pol, int(mode), outcome.ctypes.data, hops.ctypes.data,
+                                                 handler.ctypes.data, holder.ctypes.data, nxt.ctypes.data, C.byref(ms)))
+        return outcome, hops, handler, holder, nxt, ms.value
+
+    def forward_census(self, keys, max_hops=8, policy="chain", replica_points=100, mode=0):
+        """(counted, outcomes uint32 [K, 6], hops_hist uint32 [K, max_hops + 1], hist_off[K + 1], hist_handler, hist_count,
+        ms): every key entering at every live node of the cluster. outcomes[k] counts the outcomes of key k in the order
+        of FWD_OUTCOMES, hops_hist[k, j] its requests that ended after j forwards; hist_handler / hist_count
+        [hist_off[k]:hist_off[k + 1]] are the distinct handlers of key k (ascending, -1 = not served first) and the
+        entries whose request ends at each. All three sum to counted per key (swimsim.metrics.forward_availability)."""
+        pol = _forward_policy(policy, "forward_census")
+        blob, off = _pack_keys(keys)
+        K = len(off) - 1
+        H = int(max_hops)
+        cap = max(1, 2 * K)
+        while True:
+            outcomes = np.zeros((K, 6), np.uint32)
+            hist = np.zeros((K, max(H, 0) + 1), np.uint32)
+            hoff = np.zeros(K + 1, np.uint64)
+            mem, cnt = np.empty(cap, np.int32), np.empty(cap, np.uint32)
+            counted, nh, ms = C.c_uint32(), C.c_size_t(), C.c_double()
+            self._chk(load_library().swimsim_forward_census(self.h, blob, off.ctypes.data, K, int(replica_points), H, pol,
+                                                            int(mode), C.byref(counted), outcomes.ctypes.data,
+                                                            hist.ctypes.data, hoff.ctypes.data, mem.ctypes.data,
+                                                            cnt.ctypes.data, cap, C.byref(nh), C.byref(ms)))
+            if nh.value <= cap:
+                return counted.value, outcomes, hist, hoff, mem[:nh.value].copy(), cnt[:nh.value].copy(), ms.value
+            cap = nh.value
+
+    def forward_times(self):
+        """(table_ms, chase_ms, hist_ms): the device time of the last forward / forward_census call, split over the owner
+        table, the chases and (census) the rest: the keys' hashes, the pair sort and the run count"""
+        a, b, c = C.c_double(), C.c_double(), C.c_double()
+        self._chk(load_library().swimsim_forward_times(self.h, C.byref(a), C.byref(b), C.byref(c)))
+        return a.value, b.value, c.value
+
     def address(self, m):
         """member m's address (the synthetic one unless the cluster was given addresses)"""
         a = getattr(self, "_addresses", None)
@@ -1092,6 +1171,20 @@ class ShardedCluster:
     def ring_census(self, who="live", mode=0):
         return merge_ring_histograms([c.ring_census(who, mode) for c in self.shards])
 
+    # a forwarded request may visit any row: one handle must own them all (include/swimsim.h, ABI 16)
+    def _no_forward(self, what):
+        raise SwimsimError(f"EINVAL: {what}: a chain may visit any row, and chains that cross shards are not supported; "
+                           f"use a Cluster that owns every row")
+
+    def forward(self, *args, **kw):
+        self._no_forward("forward")
+
+    def forward_census(self, *args, **kw):
+        self._no_forward("forward_census")
+
+    def forward_times(self):
+        self._no_forward("forward_times")
+
     def address(self, m):
         return self.shards[0].address(m)
 
@@ -1307,3 +1400,10 @@ class Node:
     def Checksum(self):                                   # ringpop.go:571-577: the checksum of this node's own ring
         """Fingerprint32 of the addresses this node holds alive or suspect, joined by ";" (hashring.go:100-107)"""
         return int(self.c.ring_checksums([self.o])[0][0])
+
+    def HandleOrForward(self, key, max_hops=8, replica_points=100):   # ringpop.go:687-712 from this node, one attempt
+        """(handled_here, handler_address, outcome_name): whether this node handles `key` itself, the address of the node
+        that does ("" when the request is not served) and the outcome, one of swimsim.FWD_OUTCOMES"""
+        outcome, _, handler, _, _, _ = self.c.forward([key], [self.o], None, max_hops, "chain", replica_points)
+        m = int(handler[0, 0])
+        return m == self.o, (self.c.address(m) if m >= 0 else ""), FWD_OUTCOMES[int(outcome[0, 0])]

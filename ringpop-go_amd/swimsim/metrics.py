@@ -139,3 +139,59 @@ def replica_agreement(counted, hist_off, hist_member, hist_count, n) -> ReplicaA
     if (unanimous > int(n)).any():
         raise ValueError(f"replica_agreement: a key lists more than n = {n} members in every counted row")
     return ReplicaAgreement(distinct, unanimous, unanimous == distinct)
+
+
+@dataclass
+class ForwardAvailability:
+    """per key of a forward census (requests forwarded through every live node's own ring view):
+    served:      the share of the counted entries whose request is handled, LOCAL or DELIVERED (0.0: no entry counted);
+    mean_hops:   the mean number of forwards of the served requests (nan: none served). The hop bins hold every
+                 request, served or not: a HOP_LIMIT request made max_hops forwards and is taken out, an UNREACHABLE or
+                 NO_OWNER request may have ended at any hop, so for a key that has such requests the figure is an upper
+                 bound (they are taken as ending at hop 0) and hops_exact is False;
+    hops_exact:  mean_hops is exact: the key has no UNREACHABLE and no NO_OWNER request;
+    handlers:    the number of distinct nodes that handle the key;
+    split:       more than one node handles the key;
+    and the totals over all keys: requests = counted * K, served_total, outcome_totals[6] in the order of the outcome
+    codes (local, delivered, unreachable, hop_limit, no_owner, entry_down), hops_total[max_hops + 1], split_keys."""
+    served: np.ndarray
+    mean_hops: np.ndarray
+    hops_exact: np.ndarray
+    handlers: np.ndarray
+    split: np.ndarray
+    requests: int
+    served_total: int
+    outcome_totals: np.ndarray
+    hops_total: np.ndarray
+    split_keys: int
+
+
+def forward_availability(counted, outcomes, hops_hist, hist_off, hist_handler, hist_count) -> ForwardAvailability:
+    """counted, outcomes[K, 6], hops_hist[K, max_hops + 1], hist_off[K + 1], hist_handler, hist_count as forward_census()
+    returns them (handlers ascending per key, -1 = not served first)."""
+    counted = int(counted)
+    outcomes = np.asarray(outcomes, dtype=np.int64)
+    hops_hist = np.asarray(hops_hist, dtype=np.int64)
+    hist_off = np.asarray(hist_off, dtype=np.int64).reshape(-1)
+    hist_handler = np.asarray(hist_handler, dtype=np.int64).reshape(-1)
+    hist_count = np.asarray(hist_count, dtype=np.int64).reshape(-1)
+    K = len(hist_off) - 1
+    if K < 0 or outcomes.shape != (K, 6) or hops_hist.ndim != 2 or len(hops_hist) != K or hops_hist.shape[1] < 2 or \
+            len(hist_handler) != len(hist_count) or hist_off[-1] != len(hist_handler):
+        raise ValueError("forward_availability: outcomes[K, 6], hops_hist[K, max_hops + 1], hist_off[K + 1] and hist_handler / "
+                         "hist_count of hist_off[K] entries expected")
+    key = np.repeat(np.arange(K), np.diff(hist_off))
+    per_key = lambda sel: np.bincount(key[sel], weights=hist_count[sel], minlength=K).astype(np.int64)
+    good = outcomes[:, 0] + outcomes[:, 1]
+    if (outcomes.sum(axis=1) != counted).any() or (hops_hist.sum(axis=1) != counted).any() or \
+            (per_key(hist_handler >= 0) != good).any() or (per_key(hist_handler < 0) != counted - good).any():
+        raise ValueError("forward_availability: per key, the outcome bins, the hop bins and the handler counts sum to counted, "
+                         "and the handlers >= 0 take the local and delivered requests")
+    max_hops = hops_hist.shape[1] - 1
+    hops = (hops_hist * np.arange(max_hops + 1)).sum(axis=1) - max_hops * outcomes[:, 3]
+    handlers = np.bincount(key[hist_handler >= 0], minlength=K)
+    return ForwardAvailability(served=good / counted if counted else np.zeros(K),
+                               mean_hops=np.where(good > 0, hops / np.maximum(good, 1), np.nan),
+                               hops_exact=outcomes[:, 2] + outcomes[:, 4] == 0, handlers=handlers, split=handlers > 1,
+                               requests=counted * K, served_total=int(good.sum()), outcome_totals=outcomes.sum(axis=0),
+                               hops_total=hops_hist.sum(axis=0), split_keys=int((handlers > 1).sum()))
