@@ -27,6 +27,11 @@ Restrictions of the generator, each because one side cannot take the input at al
   * a clock offset k at round r has r + k >= 0 (the engine refuses a clock before t0), and add_join_list names every
     member once (MembershipAsChanges lists each member once; the engine refuses a repeat).
 No event kind and no mutator is left out.
+
+mass_case(n, seed) is the same schedule over 30 rounds from a converged start, with events that take a fraction of the
+cluster merged in (MASS_CASES: 1,100, 2,304 and 4,160 members; tests/test_fuzz_at_size_host.py on the oracle,
+tests/test_fuzz_at_size.py engine against committed oracle records, tests/fuzz_records.py the records). Every
+restriction above holds there too: the mass events are events, which both sides take on any member.
 """
 import random
 
@@ -122,6 +127,49 @@ def case(n, seed, rounds=ROUNDS):
         calls.append({"round": r, "rounds": k, "muts": muts, "events": events})
         r += k
     return {"n": n, "seed": seed, "rounds": rounds, "init": init, "options": opts, "watch": watch, "calls": calls}
+
+
+# ---- mass schedules: the same vocabulary with a fraction of the cluster taking part, at sizes past 1,024 members ----
+# (tests/test_fuzz_at_size_host.py on the oracle, tests/test_fuzz_at_size.py engine against committed oracle records)
+MASS_ROUNDS = 30
+MASS_CASES = [(1100, 0), (2304, 0), (4160, 0), (4160, 1)]
+# Round of each mass event; the leaves fall on random rounds. The kill comes before the reincarnation and the
+# reincarnation takes 97 % of the members so that a member revived at round 16 has missed nearly every other member's
+# new incarnation: it then changes more than 1,024 cells of its row in one round even at 1,100 members (1,091 on the
+# oracle; with 55 % reincarnated after the kill the most was 967).
+MASS_KILL_ROUND, MASS_REINCARNATE_ROUND, MASS_CUT_ROUND, MASS_JOIN_ROUND, MASS_HEAL_ROUND = 1, 2, 6, 13, 14
+MASS_REVIVE_ROUND, MASS_REAP_ROUND = 16, 18
+MASS_REINCARNATE_FRACTION = 0.97
+
+
+def mass_case(n, seed):
+    """case(n, seed, MASS_ROUNDS) from a converged start, with mass events merged into the calls that own their rounds,
+    after the base events of the round and in generation order: max(2, n/32) members killed, 97 % of the members
+    reincarnated, n/3 members cut off to partition label 1 and joined back, a heal on one member of the cut, every
+    second killed member revived, a reap on three observers and four leaves. Deterministic from (n, seed) alone."""
+    c = case(n, seed, MASS_ROUNDS)
+    c["init"] = "converged"
+    rng = random.Random(2_000_003 * n + seed)
+    killed = sorted(rng.sample(range(n), max(2, n // 32)))
+    reinc = sorted(rng.sample(range(n), int(MASS_REINCARNATE_FRACTION * n)))
+    cut = sorted(rng.sample(range(n), n // 3))
+    mass = [(MASS_KILL_ROUND, EV_KILL, m, 0) for m in killed]
+    mass += [(MASS_REINCARNATE_ROUND, EV_REINCARNATE, m, 0) for m in reinc]
+    mass += [(MASS_CUT_ROUND, EV_PARTITION, m, 1) for m in cut]
+    mass += [(MASS_JOIN_ROUND, EV_PARTITION, m, 0) for m in cut]
+    mass += [(MASS_HEAL_ROUND, EV_HEAL, rng.choice(cut), 0)]
+    mass += [(MASS_REVIVE_ROUND, EV_REVIVE, m, 0) for m in killed[::2]]
+    mass += [(MASS_REAP_ROUND, EV_REAP, o, 0) for o in rng.sample(range(n), 3)]
+    live = [m for m in range(n) if m not in set(killed)]
+    mass += [(rng.randrange(MASS_ROUNDS), EV_LEAVE, m, 0) for m in rng.sample(live, 4)]
+    calls = []
+    for call in c["calls"]:
+        events = []
+        for r in range(call["round"], call["round"] + call["rounds"]):
+            events += [e for e in call["events"] if e[0] == r] + [e for e in mass if e[0] == r]
+        calls.append(dict(call, events=events))
+    c["calls"] = calls
+    return c
 
 
 def without_direct_heal(c):
