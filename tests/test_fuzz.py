@@ -71,17 +71,18 @@ def compare_final(eng, ora, c, label):
     assert (eng.clock_offsets() == ora.clock_offsets()).all(), f"{where}: clock offsets"
 
 
-def run_case(eng, ora, c, label, after_call=None):
-    """the schedule on both sides, compared after every call and at the end; after_call() runs after each compared call"""
+def run_case(eng, ora, c, label, after_call=None, after_round=None):
+    """the schedule on both sides, compared after every call and at the end; after_call() runs after each compared call,
+    after_round(r) after each round of the oracle (fuzz_scenarios.oracle_call)"""
     try:
-        _run_case(eng, ora, c, label, after_call)
+        _run_case(eng, ora, c, label, after_call, after_round)
     except swimsim.SwimsimError as e:
         if "EHIP" in str(e):                                        # a device error: nothing more runs on this GPU
             pytest.exit(f"{label}: device error, the session ends here: {e}", returncode=3)
         raise
 
 
-def _run_case(eng, ora, c, label, after_call):
+def _run_case(eng, ora, c, label, after_call, after_round=None):
     for o in c["watch"]:
         eng.watch(o, "events")
         ora.watch(o, "events")
@@ -93,7 +94,7 @@ def _run_case(eng, ora, c, label, after_call):
             if "EHIP" in str(e):
                 raise
             pytest.fail(f"{label}: the engine refused: {e}\n{F.describe_call(call)}")
-        orets = F.oracle_call(ora, call)
+        orets = F.oracle_call(ora, call, after_round=after_round)
         compare_call(eng, ora, c, call, label, erets, orets)
         if after_call:
             after_call()

@@ -26,23 +26,39 @@ MODES = (0, 1, 2)
 KEYS64 = [f"key-{i}" for i in range(64)]
 
 
-def oracle_owners(ora, keys, R=100, addresses=None):
-    """owners[n, K] (int32, -1: empty ring) of every observer row of the oracle's state"""
+def oracle_owners(ora, keys, R=100, addresses=None, rows=None):
+    """owners[rows, K] (int32, -1: empty ring) of the oracle's state, every observer row by default"""
     n = ora.n
     addr = list(addresses) if addresses is not None else [swimsim.address_of(m) for m in range(n)]
     index = {a: m for m, a in enumerate(addr)}
     ost, _ = ora.rows()
-    out = np.empty((n, len(keys)), np.int32)
-    views = {}                                  # rows that hold the same members alive or suspect have the same ring
-    for o in range(n):
+    rows = list(range(n)) if rows is None else list(rows)
+    out = np.empty((len(rows), len(keys)), np.int32)
+    views = answers_of("owners", R, addr if addresses is not None else n, keys)
+    for j, o in enumerate(rows):
         present = ost[o] <= 1
         view = present.tobytes()
         if view not in views:
             ring = OracleRing(R)
             ring.add_remove_servers([addr[m] for m in np.nonzero(present)[0]], [])
             views[view] = [index[a] if ok else -1 for a, ok in (ring.lookup(key) for key in keys)]
-        out[o] = views[view]
+        out[j] = views[view]
     return out
+
+
+# The oracle ring's answers per view, kept for the session: rows that hold the same members alive or suspect have the same
+# ring, and a ring's answers are a function of (what is asked, R, the addresses, the keys, the view) alone. The states of
+# a schedule repeat most views from call to call, and its sharded and variant runs repeat all of them.
+_ANSWERS = {}
+ANSWERS_CAP = 60_000                            # views over all tables; past it the tables start again
+
+
+def answers_of(what, R, addresses, keys):
+    """the table {view bytes: answers} of one question; addresses = the address list, or n for the synthetic ones"""
+    if sum(len(t) for t in _ANSWERS.values()) > ANSWERS_CAP:
+        _ANSWERS.clear()
+    ident = (what, R, addresses if isinstance(addresses, int) else tuple(addresses), tuple(keys))
+    return _ANSWERS.setdefault(ident, {})
 
 
 def cascade_keys(wl):

@@ -19,7 +19,7 @@ import swimsim
 from swimsim import metrics
 from swimsim import workloads as W
 from test_census import make_pair, scenario_eviction, scenario_self_only, step_both
-from test_route import KEYS64, MODES, cascade_keys, live_mask, mid_cascade
+from test_route import KEYS64, MODES, answers_of, cascade_keys, live_mask, mid_cascade
 
 pytestmark = pytest.mark.gpu
 
@@ -32,7 +32,7 @@ def oracle_prefs(ora, keys, n, R=100, addresses=None, rows=None):
     rows = list(range(ora.n)) if rows is None else list(rows)
     out = np.full((len(rows), len(keys), n), -1, np.int32)
     srv = np.zeros(len(rows), np.uint32)
-    views = {}                                  # rows that hold the same members alive or suspect have the same ring
+    views = answers_of(("prefs", n), R, addr if addresses is not None else ora.n, keys)   # (kept for the session)
     for j, o in enumerate(rows):
         present = ost[o] <= 1
         view = present.tobytes()
