@@ -28,7 +28,8 @@
 extern "C" {
 #endif
 
-#define SWIMSIM_ABI_VERSION 16   /* 16: swimsim_forward, swimsim_forward_census and swimsim_forward_times (read-only; the
+#define SWIMSIM_ABI_VERSION 17   /* 17: swimsim_tuning.slot_bump and the unit "bump_by_slot" (results unchanged).
+                                    16: swimsim_forward, swimsim_forward_census and swimsim_forward_times (read-only; the
                                     results of every earlier call unchanged).
                                     15: swimsim_ring_checksums, swimsim_ring_census and swimsim_ring_times (read-only; the
                                     results of every earlier call unchanged).
@@ -129,11 +130,18 @@ typedef struct swimsim_tuning {
                                  tuning block): yes; the entry is still counted, bumped and deleted as before, only its
                                  record is not written. 0 (also what an older caller's zero-initialised struct reads):
                                  every kept record is written, as before ABI 14. Results are identical either way */
+    int32_t slot_bump;        /* bump by slot (ABI 17): may a sender whose message was a walk of its hot slots
+                                 bump its piggyback counters from a bitmap of the slots it sent (one bit per slot, written
+                                 at issue) instead of reading its records back from the pool? -1 or 1 (default, also with
+                                 a NULL tuning block): yes; every other message is bumped from its records. 0 (also what
+                                 an older caller's zero-initialised struct reads): every bump reads the records, as before
+                                 ABI 17, and no bitmap is allocated. Results are identical either way */
 } swimsim_tuning;
 /* Environment, read at swimsim_create (A/B experiments; results are identical either way): SWIMSIM_SYNC_SPIN=0 waits for
  * the main stream's host round trips in the runtime's stream wait instead of polling an event; SWIMSIM_SIDE2=0 runs both
  * generations of side-stream checksum launches on one stream; SWIMSIM_CS_DEFER=0|1|2 overrides
- * swimsim_tuning.cs_defer; SWIMSIM_RESP_ECHO=0|1 overrides swimsim_tuning.resp_echo; SWIMSIM_CS_DEFER_LOG=1 writes one stderr line per phase C that had a round to leave its rows
+ * swimsim_tuning.cs_defer; SWIMSIM_RESP_ECHO=0|1 overrides swimsim_tuning.resp_echo;
+ * SWIMSIM_SLOT_BUMP=0|1 overrides swimsim_tuning.slot_bump; SWIMSIM_CS_DEFER_LOG=1 writes one stderr line per phase C that had a round to leave its rows
  * to (round, dirty rows, rows written in the round, deferred decisions, carried or hashed). */
 
 /* Events applied in phase E of a round (docs/ROUND_SEMANTICS.md §4). */
@@ -620,10 +628,12 @@ int swimsim_enable_timing(swimsim_t *h, int32_t enable);
  * swimsim_tuning.resp_echo): direct-ping response records that were kept ("recv_issued" counts them, as do the protocol
  * counter msg_changes and the bump) but not written, being echoes; "resp_merged" no longer counts them, so that
  * resp_merged with resp_echo 0 = resp_merged + resp_echoed with resp_echo 1, and the "alg bytes" of the recv_merge and
- * resp_merge families count fewer processed records than before ABI 14. The last three (ABI 11, lazy phase C,
+ * resp_merge families count fewer processed records than before ABI 14. Three for lazy phase C (ABI 11,
  * swimsim_tuning.cs_defer): "cs_skipped_rounds" = rounds whose phase C hashed nothing, "cs_carried_rows" = the dirty rows
  * they left, summed over those rounds, "cs_forced" = rounds that would have skipped but deferred too many full-sync
- * decisions and hashed */
+ * decisions and hashed. The last one, "bump_by_slot" (ABI 17, swimsim_tuning.slot_bump): the bumps (one per sender message;
+ * one per failed helper in phase Q3) taken from the sender's bitmap of sent slots instead of its records; "resp_bumped"
+ * counts the records of every bumped direct-ping message either way */
 int swimsim_kernel_units(swimsim_t *h, const char **names, double *values, size_t cap, size_t *n);
 /* profiler window marker: one tiny kernel (k_profile_mark) on the engine's stream, after the side stream drained */
 int swimsim_profile_mark(swimsim_t *h, uint32_t id);

@@ -57,7 +57,9 @@ enum Counter {
     C_X_ISSUE_SNAPS, C_X_LAZY_LATE, C_X_LAZY_MAT,
     // direct-ping response records IssueAsReceiver kept (counted, bumped) but did not write: echoes of what the sender
     // had just sent (phase D only, the responses C_X_MERGED_R counts on the other side)
-    C_X_ECHO, C_NALL
+    C_X_ECHO,
+    // bumps (sender messages) that k_resp / k_resolve took through the sender's bitmap of sent slots (DS::sbm)
+    C_X_BUMP_SLOT, C_NALL
 };
 
 constexpr int CTR_SHARDS = 64, CTR_STRIDE = 64;   // d.ctr is [CTR_SHARDS][CTR_STRIDE] u64
@@ -180,6 +182,13 @@ struct DS {
     // issue-time row needs beside the words, the checksum string's length and last included member at issue
     uint32_t *ilen;           // [NL]
     int32_t *ilast;           // [NL]
+    // bump by slot: the hot slots a sender's hot walk sent, one bit per slot, written by k_issue from the
+    // walk's keep ballots, and the row's validity word: the slots in use when the walk ran, 0 = the row's last message
+    // was no hot walk (or was empty): its bump reads the records. k_resp and k_resolve bump the sender's cells from the
+    // bitmap, whose words load beside the cells instead of after the message's records. nullptr: off
+    // (swimsim_tuning.slot_bump 0, or no hot columns)
+    unsigned long long *sbm;  // [NL][HP / 64]
+    uint32_t *sbv;            // [NL]
 };
 // entries of a row's undo log. A row of the 65,536-member cascade applies at most about 655 changes in a receive phase
 // (one per killed member), so no log of the flagship workload overflows; 10 KB per row beside the row's 1.3 MB. The

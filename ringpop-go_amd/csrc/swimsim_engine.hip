@@ -467,6 +467,7 @@ struct swimsim {
     uint32_t round_deferred = 0;                  // full-sync decisions the current round's phases D and Q2 deferred
     bool cs_carried = false;                      // some row is dirty because a phase C skipped it
     int resp_echo = 1;                            // swimsim_tuning.resp_echo: echoed response records are left out (k_recv)
+    int slot_bump = 1;                            // swimsim_tuning.slot_bump: senders bump from their bitmap of sent slots
     bool cs_defer_log = false;                    // SWIMSIM_CS_DEFER_LOG=1: one stderr line per phase C that could skip
     uint64_t cs_skipped_rounds = 0, cs_carried_rows = 0, cs_forced = 0, cs_units_base[3] = {0, 0, 0};
     bool colx_stale = false;                     // raw row writes marked every column: rebuilt at the next step
@@ -1063,6 +1064,7 @@ void hot_reset(swimsim *h, bool flush) {
     hipMemsetAsync(h->d.hidx, 0xFF, (size_t)h->N * 4, h->s);
     hipMemsetAsync(h->d.hotnew, 0, (size_t)h->d.NBIT * 4, h->s);
     hipMemsetAsync(h->d.hot_cnt, 0, 8, h->s);
+    if (h->d.sbv) hipMemsetAsync(h->d.sbv, 0, (size_t)h->NL * 4, h->s);   // (no bitmap of sent slots outlives its slots)
     hipLaunchKernelGGL(k_nhe_reset, dim3(blocks_for_threads(h->NL)), dim3(256), 0, h->s, h->d);   // every entry is cold
 }
 
@@ -1909,6 +1911,12 @@ int swimsim_create(const swimsim_config *cfg, swimsim_t **out) {
         h->err = "swimsim_tuning.resp_echo is -1, 0 or 1";
         return bail(SWIMSIM_EINVAL);
     }
+    if (tun && tun->slot_bump >= 0) h->slot_bump = tun->slot_bump;
+    if (const char *v = getenv("SWIMSIM_SLOT_BUMP")) h->slot_bump = atoi(v);   // (experiment: 0 = every bump reads the records)
+    if (h->slot_bump < 0 || h->slot_bump > 1) {
+        h->err = "swimsim_tuning.slot_bump is -1, 0 or 1";
+        return bail(SWIMSIM_EINVAL);
+    }
     if (h->fault_inject & 32) h->csr_ecap = 24;      // (tests: rows whose exception entries end within CSR_EREG of the cap)
     if (h->fault_inject & 256) h->csr_side_min = 1024;   // (tests: side launches of 1,024 rows and more take the path)
     if (const char *v = getenv("SWIMSIM_SYNC_SPIN")) h->sync_spin = atoi(v) != 0;   // (experiment: 0 = the runtime's wait)
@@ -1955,6 +1963,15 @@ int swimsim_create(const swimsim_config *cfg, swimsim_t **out) {
         hp = std::min<uint32_t>((hp + 63) & ~63u, RT_MAXSLOTS);   // (a change record's tag names at most RT_MAXSLOTS)
         d.hidx = nullptr; d.hlist = nullptr; d.hmw = nullptr; d.hde = nullptr; d.hotnew = nullptr; d.hot_cnt = nullptr;
         d.HP = 0;
+        d.sbm = nullptr; d.sbv = nullptr;
+        // bump by slot: one bit per hot slot per row (256 B a row at 2,048 slots, 16 MB at 65,536 rows)
+        // and a validity word per row. One buffer serves both modes of k_issue: phase R consumes the direct pings'
+        // bitmaps (k_resp) before phase Q1 issues again, and Q3 (k_resolve) consumes those before the next round's I.
+        if (hp && h->slot_bump) {
+            if ((rc = dalloc(h, &d.sbm, (size_t)h->NL * (hp / 64), "sent-slot bitmaps")) ||
+                (rc = dalloc(h, &d.sbv, h->NL, "sent-slot bitmap validity")))
+                return bail(rc);
+        }
         if (hp) {
             if ((rc = dalloc(h, &d.hidx, h->N, "hot index")) || (rc = dalloc(h, &d.hlist, hp, "hot list")) ||
                 (rc = dalloc(h, &d.hmw, (size_t)h->NL * hp, "hot member words")) ||
@@ -3148,13 +3165,13 @@ int swimsim_kernel_units(swimsim_t *h, const char **names, double *values, size_
                                "dense_heal", "defer", "defer_eq", "defer_norow", "defer_rep", "defer_undo",
                                "defer_rep_diff", "defer_undo_diff", "defer_fs", "defer_undo_over", "defer_clean",
                                "issue_snaps", "lazy_late", "lazy_mat", "resp_echoed",
-                               "cs_skipped_rounds", "cs_carried_rows", "cs_forced"};
+                               "cs_skipped_rounds", "cs_carried_rows", "cs_forced", "bump_by_slot"};
     const int ki[] = {C_X_CS_ROWS, C_X_CS_ROWS_N, C_X_CS_DUP, C_X_MERGED, C_X_APPLIED, C_X_RISSUED, C_X_RCALLS,
                       C_X_MERGED_R, C_X_APPLIED_R, C_X_BUMPED, C_X_ISSUED, -1, -2, C_X_DENSE_RESP, C_X_DENSE_JOBS,
                       C_X_JOBS_APPLIED, C_X_DENSE_HEAL, C_X_DEFER, C_X_DEFER_EQ, C_X_DEFER_NOROW, C_X_DEFER_REP,
                       C_X_DEFER_UNDO, C_X_DEFER_REP_DIFF, C_X_DEFER_UNDO_DIFF, C_X_DEFER_FS, C_X_DEFER_UNDO_OVER,
                       C_X_DEFER_CLEAN, C_X_ISSUE_SNAPS, C_X_LAZY_LATE, C_X_LAZY_MAT, C_X_ECHO,
-                      -3, -4, -5};                                 // (-3..-5: lazy phase C, host counts)
+                      -3, -4, -5, C_X_BUMP_SLOT};                  // (-3..-5: lazy phase C, host counts)
     const uint64_t lazy_c[3] = {h->cs_skipped_rounds - h->cs_units_base[0], h->cs_carried_rows - h->cs_units_base[1],
                                 h->cs_forced - h->cs_units_base[2]};
     static_assert(sizeof(kn) / sizeof(kn[0]) == sizeof(ki) / sizeof(ki[0]), "one counter per name");

@@ -575,6 +575,68 @@ __device__ __forceinline__ void wave_bump_pre(const DS &d, uint32_t ol, const Ms
     __threadfence_block();
 }
 
+// bumpPiggybackCounters of a hot-walk message from the sender's bitmap of sent slots (DS::sbm, DESIGN.md §3, bump by
+// slot) instead of its records: the members of the message are the set bits, and the bitmap's words, the cells and the
+// members of the slots are all addressed from the row alone, so they load in one round trip, SB_U groups of 64 slots at a
+// time (768 slots, 2 registers a group beside the one load of the groups' words; a longer row loops). nslots is the row's validity word: the slots in use when
+// the walk ran, which is the number in use now (slots are assigned only before phase I). A sent slot whose cell reads
+// "no entry" now was deleted since (the row's own receive wave): skipped, as the reference's !ok (disseminator.go:
+// 139-141); a cell replaced since is bumped like any other. Every sent member is hot, so d.nhe is untouched. Returns the
+// wave's deleted entries.
+constexpr int SB_U = 12;
+__device__ __forceinline__ int wave_bump_slots(const DS &d, uint32_t ol, uint32_t nslots, int maxp) {
+    uint32_t *hx = (uint32_t *)(d.hde + (size_t)ol * d.HP);        // word 0 of each hot cell, stride 2
+    const unsigned long long *bm = d.sbm + (size_t)ol * (d.HP / 64);
+    int del = 0;
+    for (uint32_t base = 0; base < nslots; base += 64 * SB_U) {
+        uint32_t x[SB_U], m[SB_U];
+        // (lane u loads the word of group u: one load for the SB_U groups, read from its lane below)
+        const uint32_t g = (base >> 6) + lane_id();
+        const unsigned long long wl = lane_id() < (uint32_t)SB_U && g * 64 < nslots ? bm[g] : 0ull;
+#pragma unroll
+        for (int u = 0; u < SB_U; u++) {
+            const uint32_t k = base + u * 64 + lane_id();
+            x[u] = k < nslots ? hx[(size_t)k * 2] : DE_NONE;
+            m[u] = k < nslots ? d.hlist[k] : 0u;
+        }
+#pragma unroll
+        for (int u = 0; u < SB_U; u++) {
+            const uint32_t k = base + u * 64 + lane_id();
+            const uint32_t p = de_p(x[u]);
+            const uint32_t wlo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)wl, u);
+            const uint32_t whi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(wl >> 32), u);
+            const uint32_t wh = lane_id() < 32 ? wlo : whi;         // (the half that holds this lane's bit)
+            if (!((wh >> (lane_id() & 31)) & 1u) || p == DP_NONE) continue;
+            uint32_t nx;
+            if ((int)(p + 1) >= maxp) {
+                nx = x[u] | 0xFF000000u;
+                atomicAnd(&d.dbit[(size_t)ol * d.NBIT + (m[u] >> 5)], ~(1u << (m[u] & 31)));
+                del++;
+            } else {
+                nx = x[u] + (1u << 24);
+            }
+            hx[(size_t)k * 2] = nx;
+        }
+    }
+    return wsum(del);
+}
+// is the bump of message md of row ol taken from the bitmap? (sbn: the row's validity word, 0 when the path is off)
+__device__ __forceinline__ bool bump_by_slot(const MsgDesc &md, uint32_t sbn) { return sbn && md.kind == 0 && md.len; }
+__device__ void wave_bump_slot(const DS &d, uint32_t ol, uint32_t nslots) {
+    const int del = wave_bump_slots(d, ol, nslots, d.maxp[ol]);
+    if (lane_id() == 0) {
+        if (del) d.dcnt[ol] -= del;
+        ctr_add(d, C_X_BUMP_SLOT, 1ull);
+    }
+    __threadfence_block();
+}
+__device__ __forceinline__ void wave_bump_slot_pre(const DS &d, uint32_t ol, uint32_t nslots, RowPre &p) {
+    const int del = wave_bump_slots(d, ol, nslots, p.maxp);
+    if (del) { p.dcnt -= del; if (lane_id() == 0) d.dcnt[ol] = p.dcnt; }
+    if (lane_id() == 0) ctr_add(d, C_X_BUMP_SLOT, 1ull);
+    __threadfence_block();
+}
+
 // The message pool is split into POOL_SHARDS sub-pools with a cursor each (own 128-B line): one returning
 // atomic per issuing wave on a single word saturates at ~88 per us (MI355X_MICROARCH.md row "dequeue"), which
 // serialised the 65,536 issues of a cascade round. A wave starts at the sub-pool of its wave id and moves on
@@ -628,12 +690,13 @@ __device__ __forceinline__ uint32_t wscan_excl(uint32_t v, uint32_t &total) {
 // returns the entries kept, and for RECV the deleted entries in del / delnh, wave sums. echo (RECV only, or null): the
 // receive wave's bitmap of hot slots whose kept entry is an echo (wave_merge_body): such an entry is counted as kept,
 // bumped and deleted like any other, but its record is not written and takes no position, so out.len, the records
-// written, may be below the entries kept)
+// written, may be below the entries kept. sent (the sender's hot walk only, or null): the row's bitmap of sent slots,
+// DS::sbm: word g takes the keep ballot of slots 64 g .. 64 g + 63, for every group below nslots)
 template <bool RECV>
 __device__ __forceinline__ uint32_t wave_issue_body(const DS &d, uint32_t ol, uint32_t sender, uint32_t sinc, MsgDesc &out,
                                                     uint32_t cnt, int maxp, bool hotwalk, uint32_t nslots,
                                                     unsigned long long off, int &del_out, int &delnh_out,
-                                                    const uint32_t *echo = nullptr) {
+                                                    const uint32_t *echo = nullptr, unsigned long long *sent = nullptr) {
     const size_t rb = (size_t)ol * d.NP, hb = (size_t)ol * d.HP;
     uint32_t *bits = d.dbit + (size_t)ol * d.NBIT;
     uint32_t pos = 0;                                              // records written
@@ -669,6 +732,15 @@ __device__ __forceinline__ uint32_t wave_issue_body(const DS &d, uint32_t ol, ui
             }
             uint32_t tot;
             uint32_t at = pos + wscan_excl(nk, tot);
+            if (!RECV && sent) {                                   // the sent slots of each 64-slot group, one word:
+                unsigned long long kb = 0;                         // lane u stores group u's ballot, one store a batch
+#pragma unroll
+                for (int u = 0; u < MB; u++) {
+                    const unsigned long long b = __ballot(keep[u]);
+                    if (lane_id() == (uint32_t)u) kb = b;
+                }
+                if (lane_id() < (uint32_t)MB && base + lane_id() * 64 < nslots) sent[(base >> 6) + lane_id()] = kb;
+            }
 #pragma unroll
             for (int u = 0; u < MB; u++) {
                 if (!keep[u]) continue;
@@ -868,19 +940,28 @@ __device__ __forceinline__ uint32_t wave_issue_body(const DS &d, uint32_t ol, ui
     return skip ? min((uint32_t)wsum((int)kept), cnt) : out.len;
 }
 
+// (mark: the message is a phase's request, k_issue: the row's bitmap of sent slots and its validity word are written on
+// every path, so a bitmap of an earlier message of the row is never read as this one's, DS::sbm)
 template <bool RECV>
-__device__ uint32_t wave_issue_t(const DS &d, uint32_t ol, uint32_t sender, uint32_t sinc, MsgDesc &out) {
+__device__ uint32_t wave_issue_t(const DS &d, uint32_t ol, uint32_t sender, uint32_t sinc, MsgDesc &out, bool mark = false) {
     // (the row's reads in one round trip, before the pool allocation's returning atomic)
     const uint32_t cnt = (uint32_t)d.dcnt[ol];
     const int maxp = RECV ? d.maxp[ol] : 0;
     const bool hotwalk = d.hidx && d.nhe[ol] == 0;
     const uint32_t nslots = d.hidx ? d.hot_cnt[0] : 0u;
+    mark = mark && !RECV && d.sbm;
     out.kind = 0; out.len = 0; out.off_lo = out.off_hi = 0;
-    if (cnt == 0) return 0;
-    const unsigned long long off = pool_alloc(d, cnt);
-    if (off == ~0ull) return 0;
+    const unsigned long long off = cnt ? pool_alloc(d, cnt) : ~0ull;
+    if (off == ~0ull) {                                             // (an empty buffer, a full pool: nothing to bump)
+        if (mark && lane_id() == 0) d.sbv[ol] = 0u;
+        return 0;
+    }
     int del = 0, delnh = 0;
-    const uint32_t n = wave_issue_body<RECV>(d, ol, sender, sinc, out, cnt, maxp, hotwalk, nslots, off, del, delnh);
+    unsigned long long *sent = mark && hotwalk ? d.sbm + (size_t)ol * (d.HP / 64) : nullptr;
+    const uint32_t n = wave_issue_body<RECV>(d, ol, sender, sinc, out, cnt, maxp, hotwalk, nslots, off, del, delnh, nullptr,
+                                             sent);
+    // (valid only when every kept slot's record was written: the bitmap then names the members of the message exactly)
+    if (mark && lane_id() == 0) d.sbv[ol] = sent && out.len == cnt ? nslots : 0u;
     if (RECV) {
         if (lane_id() == 0 && del) d.dcnt[ol] -= del;
         if (lane_id() == 0 && delnh) d.nhe[ol] -= delnh;
@@ -890,7 +971,9 @@ __device__ uint32_t wave_issue_t(const DS &d, uint32_t ol, uint32_t sender, uint
 }
 
 // issueChanges / IssueAsSender (disseminator.go:128-133,201-215): snapshot of every entry
-__device__ void wave_issue(const DS &d, uint32_t ol, MsgDesc &out) { wave_issue_t<false>(d, ol, 0, 0, out); }
+__device__ void wave_issue(const DS &d, uint32_t ol, MsgDesc &out, bool mark = false) {
+    wave_issue_t<false>(d, ol, 0, 0, out, mark);
+}
 
 // IssueAsReceiver up to the full-sync decision (disseminator.go:156-199). Returns kept count.
 __device__ uint32_t wave_issue_recv(const DS &d, uint32_t ol, uint32_t sender, uint32_t sinc, MsgDesc &out) {
@@ -1381,7 +1464,7 @@ __global__ void k_issue(DS d, int mode, const int32_t *tgt, const uint8_t *faile
     const uint32_t clen = d.clen[ol];
     const int32_t clast = d.clast[ol];
     MsgDesc md;
-    wave_issue(d, ol, md);
+    wave_issue(d, ol, md, true);                                    // (and the row's bitmap of sent slots, DS::sbm)
     uint32_t slot = SRC_NONE;
     if (sS && dirty && !d.ulog) {                                   // (no undo log: the row is copied)
         MsgDesc sn;
@@ -2139,9 +2222,11 @@ __global__ void k_resp(DS d, const int32_t *tgt, const uint8_t *failed, const Ms
     RowPre p = row_pre(d, ol);
     const uint32_t now = wave_clock(d, o, r);
     const MsgDesc sd = sdesc[o], rd = rdesc[o];
+    const uint32_t sbn = d.sbv ? uni(d.sbv[ol]) : 0u;               // (k_issue wrote it for every sender of phase I)
     uint4 rec0[MB];                                                 // (the response's first records ride with the bump's
     merge_first(d, rd, rec0);                                       // loads: the pool is read-only here)
-    wave_bump_pre(d, ol, sd, p);
+    if (bump_by_slot(sd, sbn)) wave_bump_slot_pre(d, ol, sbn, p);   // (a hot walk's message: from its bitmap of sent slots)
+    else wave_bump_pre(d, ol, sd, p);
     if (rd.kind != 0 || rd.len)                                    // (an empty response: no merge, no reductions)
         wave_merge_msg_pre(d, ol, o, rd, now, now, 1, p, C_X_DENSE_RESP, rec0);
     if (lane_id() == 0) {
@@ -2158,11 +2243,15 @@ __global__ void k_resolve(DS d, const int32_t *tgt, const uint8_t *failed, const
     const uint32_t o = d.lo + ol, K = d.K;
     const uint32_t now = wave_clock(d, o, r);
     uint32_t errs = 0;
+    const MsgDesc sd = sdesc2[o];
+    const uint32_t sbn = d.sbv ? uni(d.sbv[ol]) : 0u;               // (k_issue wrote it for every sender of phase Q1)
     for (uint32_t q = 0; q < nh[ol]; q++) {
         const uint32_t h = H[(size_t)ol * K + q];
         if (!reach(d, o, h)) {
             errs++;
-            wave_bump(d, ol, sdesc2[o]);                            // bump only on error (105-106)
+            // bump only on error (105-106); a hot walk's message from its bitmap of sent slots, once per failed helper
+            if (bump_by_slot(sd, sbn)) wave_bump_slot(d, ol, sbn);
+            else wave_bump(d, ol, sd);
         } else {
             const MsgDesc rd = rdesc2[(size_t)o * K + q];
             if (rd.kind != 0 || rd.len) wave_merge_msg(d, ol, o, rd, now, now, 2, C_X_DENSE_RESP);

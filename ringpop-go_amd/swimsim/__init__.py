@@ -69,7 +69,7 @@ class Tuning(C.Structure):
     _fields_ = [("hot_slots", C.c_int32), ("dense_slots", C.c_int32), ("cs_async", C.c_int32),
                 ("cs_async_rows", C.c_int32), ("cs_narrow_rows", C.c_int32), ("cs_ref", C.c_int32),
                 ("fault_inject", C.c_int32), ("defer_test", C.c_int32), ("cs_defer", C.c_int32),
-                ("resp_echo", C.c_int32)]
+                ("resp_echo", C.c_int32), ("slot_bump", C.c_int32)]
 
 
 def make_tuning(tuning):
